@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- headline measurement of the MI355X quantized decode hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-extra]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (the headline and its `roofline`);
+`--dump-outputs DIR` also writes the output of the last timed step.  Every other measurement (the cold timing,
+`cpu_baseline*`, `extra`) is made only with `--full`.
 
 One "step" = one pass of the hot path over one batch of synthetic input: a
 paged-attention decode call (through torch.ops -> C ABI -> HIP) on
@@ -12,14 +16,18 @@ Inputs are resident in HBM before the timed region.  `value` = algorithmic bytes
 Steady state: a fresh process runs its first ~180 decode launches (~15 ms) 3-4 % slower than every
 launch after them (tools/decode_drift.py, profiles/r02_decode_drift.txt), so ~100 ms of untimed
 launches precede the W warmup steps (`roofline.steady_state`); the graph-timed legs of `extra`
-replay ~25 ms before their timed replays for the same reason.
+replay ~25 ms before their timed replays for the same reason.  `ms_per_step` = wall time of the K timed
+steps / K.
+
+--dump-outputs DIR: rank 0 writes DIR/decode_out.npy, the [64, 32, 128] attention output of the last timed
+step as float32 (1 MiB).  Inputs come from a fixed seed, so two builds can be compared output for output.
 
 N > 1: one rank per GPU, either launched by torch.distributed.run (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the env) or, when WORLD_SIZE is not set, by this script itself:
 `python bench.py --gpus N` spawns its N ranks before it touches a GPU and exits non-zero if
 any rank fails or the RCCL world is not N.  Attention shards by KV head with no collective
 (SURVEY.md 8e): the headline keeps the per-GPU configs[1] shape on every rank ("weak" scaling);
-value = bytes of all ranks / max time.  `extra` then carries, timed over all ranks (max):
+value = bytes of all ranks / max time.  With --full `extra` then carries, timed over all ranks (max):
   configs4_strong   configs[4] (8 x 128k, 64q/8kv, fp8) with heads / N per rank: strong scaling
   configs3_per_gpu  configs[3] per-GPU attention shape (256 x 32k, 8q/1kv) on every rank
   custom_all_reduce peer-to-peer all-reduce vs RCCL, 256 KiB / 4 MiB (result-checked first; VLLM_AMD_BENCH_CUSTOM_AR=0 skips)
@@ -27,7 +35,8 @@ value = bytes of all ranks / max time.  `extra` then carries, timed over all ran
                     RCCL all-reduce (us, bus GB/s)
 
 The JSON line also carries
-  roofline      dominant kernel vs the 8 TB/s HBM3E peak, HIP-event timed
+  roofline      dominant kernel vs the 8 TB/s HBM3E peak, HIP-event timed (`roofline.cold`: --full)
+and with --full
   cpu_baseline  the reference's own CPU paged_attention_v1 (oracle/_ref, built
                 from /root/reference/csrc/cpu by oracle/Makefile) on configs[0],
                 timed on the host cores of this box; falls back to our C port
@@ -175,29 +184,34 @@ def time_gpu_graph(fn, iters, replays=5):
     return e0.elapsed_time(e1) * 1e-3 / (iters * replays)
 
 
-def run_attention(cfg, steps, warmup, device, dist=None, version="auto"):
+def run_attention(cfg, steps, warmup, device, dist=None, version="auto", cold=False):
     from vllm_amd import _custom_ops as ops
     from vllm_amd.attention.paged_attn import PagedAttention
     S, ctx, H, KVH, D, BS = cfg["S"], cfg["ctx"], cfg["H"], cfg["KVH"], cfg["D"], cfg["BS"]
     fp8 = cfg["kv"] == "fp8"
     q, caches, bt, sl, one = make_attention_inputs(S, ctx, H, KVH, D, BS, fp8, device)
     kvd = "fp8" if fp8 else "auto"
-    state = {"i": 0}
+    state = {"i": 0, "last": -1}
 
     def step():
         kc, vc = caches[state["i"] % len(caches)]
         state["i"] += 1
-        return PagedAttention.forward_decode(q, kc, vc, bt, sl, ctx, kvd, KVH, D ** -0.5, None,
-                                             one, one)
+        out = PagedAttention.forward_decode(q, kc, vc, bt, sl, ctx, kvd, KVH, D ** -0.5, None,
+                                            one, one)
+        if state["i"] == state["last"]:     # only the last timed step's output is kept (--dump-outputs): holding
+            state["out"] = out              # every step's would make the allocator alternate output buffers
+        return out
 
-    # cold: exactly the driver's W warmups + K timed steps as the first launches of the process ...
-    cold_wall, cold_ev = time_gpu(step, steps, warmup, dist)
+    # cold (--full): exactly the driver's W warmups + K timed steps as the first launches of the process ...
+    cold_wall, cold_ev = time_gpu(step, steps, warmup, dist) if cold else (None, None)
     # ... and the steady state: the same W + K after ~100 ms of untimed launches
+    state["i"] = 0      # (precondition makes a multiple of 50 launches: the last timed step reads the same cache in every run)
     pre = precondition(step)
+    state["last"] = state["i"] + warmup + steps
     wall, ev = time_gpu(step, steps, warmup, dist)
     nbytes = attention_bytes(S, ctx, H, KVH, D, BS, 1 if fp8 else 2)
     return dict(wall=wall, event=ev, bytes=nbytes, precondition_launches=pre, cold_wall=cold_wall,
-                cold_event=cold_ev)
+                cold_event=cold_ev, out=state["out"])
 
 
 def run_attention_shape(name, S, ctx, H, KVH, device, dist=None, world=1, iters=20, D=128, BS=16):
@@ -699,16 +713,23 @@ def dry_run(args):
     return 0 if ok else 2
 
 
-def main():
+def main(argv=None):
+    """`argv`: the argument list of an in-process call (tests), one GPU only: the ranks of --gpus N > 1 are
+    started with the process's own command line."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks = GPUs (default: WORLD_SIZE, else 1)")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-extra", action="store_true", help="skip scaled_mm / cache / cpu legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/decode_out.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the cold timing, the CPU baselines and `extra` (other ops, shapes, N > 1 legs)")
     ap.add_argument("--dry-run-backend", default=None,
                     help="(tests) 'gloo': ranks only rendezvous on the CPU and rank 0 prints a stub line")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
 
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -752,10 +773,15 @@ def main():
 
     # configs[1]; per-GPU shape is the same at every N (head-sharded, weak scaling)
     cfg = dict(S=64, ctx=4096, H=32, KVH=8, D=128, BS=16, kv="fp8")
-    r = run_attention(cfg, args.steps, args.warmup, device, dist)
+    r = run_attention(cfg, args.steps, args.warmup, device, dist, cold=args.full)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "decode_out.npy"), r["out"].float().cpu().numpy())
     wall = r["wall"]
     if use_dist:
-        t = torch.tensor([wall, r["event"], r["cold_wall"], r["cold_event"]], dtype=torch.float64, device=device)
+        t = torch.tensor([wall, r["event"], r["cold_wall"] or 0.0, r["cold_event"] or 0.0], dtype=torch.float64,
+                         device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall, ev, cold_wall, cold_ev = t.tolist()
     else:
@@ -786,7 +812,6 @@ def main():
             if trace_us:
                 trace_src = "profiles/" + name + " (committed rocprofv3 --kernel-trace run, not this run)"
                 break
-    cold_per = cold_ev / args.steps
 
     line = {
         "metric": "paged-attn decode HBM GB/s (% peak) + fp8 scaled_mm TFLOPS at 1/2/4/8 GPUs",
@@ -818,18 +843,20 @@ def main():
                                                 if trace_cold_us else None),
                      "kernel_trace_avg_us": trace_us, "kernel_trace_cold_avg_us": trace_cold_us,
                      "kernel_trace_source": trace_src,
-                     "cold": {"what": f"the process's first {args.warmup} + {args.steps} launches (no "
-                                      "preconditioning): W warmups, K timed",
-                              "us_per_launch": round(cold_per * 1e6, 2),
-                              "frac": round(r["bytes"] / cold_per / 1e9 / HBM_PEAK_GBPS, 4),
-                              "value_gbps": round(total_bytes / cold_wall / 1e9, 1)},
                      "algorithmic_bytes_per_launch": r["bytes"],
                      "steady_state": f"{r['precondition_launches']} untimed launches (~{PRECONDITION_MS:.0f} ms) before "
                                      f"the {args.warmup} warmup steps: the first ~200 launches of a process run "
                                      "3-4 % slower (tools/decode_drift.py)"},
     }
 
-    if rank == 0 and not args.no_extra:
+    if args.full:
+        cold_per = cold_ev / args.steps
+        line["roofline"]["cold"] = {"what": f"the process's first {args.warmup} + {args.steps} launches (no "
+                                            "preconditioning): W warmups, K timed",
+                                    "us_per_launch": round(cold_per * 1e6, 2),
+                                    "frac": round(r["bytes"] / cold_per / 1e9 / HBM_PEAK_GBPS, 4),
+                                    "value_gbps": round(total_bytes / cold_wall / 1e9, 1)}
+    if rank == 0 and args.full:
         extra = {}
         if world == 1:
             shapes = [(4096, 6144), (4096, 4096), (4096, 28672), (14336, 4096)]
@@ -856,7 +883,7 @@ def main():
             # same workload as `value` (fp8 KV), which the reference's CPU kernel cannot run
             line["cpu_baseline_port"] = cpu_baseline_port()
         line["extra"] = extra
-    if use_dist:
+    if use_dist and args.full:
         from vllm_amd.distributed import bench_row_parallel
         ex = {}
         try:
@@ -883,6 +910,7 @@ def main():
             ca = run_custom_ar_children(rank, local_rank, world)
             if rank == 0:
                 line.setdefault("extra", {})["custom_all_reduce"] = ca
+    if use_dist:
         dist.barrier()
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -32,7 +32,7 @@
 // STATUS: logic-tested with simulated ranks (one process, one stream per rank, one GPU) and with
 // two processes sharing one GPU through IPC handles; never run across GPUs (the development box
 // has one).  Off by default: tensor_model_parallel_all_reduce uses RCCL unless asked otherwise;
-// `bench.py --gpus N` runs it beside RCCL, result-checked first.
+// `bench.py --gpus N --full` runs it beside RCCL, result-checked first.
 #include "common.cuh"
 
 #include <string.h>

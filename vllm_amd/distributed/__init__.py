@@ -137,7 +137,7 @@ def bench_row_parallel(device, dist, M: int = 256, hidden: int = 8192, iters: in
 
 def bench_custom_all_reduce(device, dist, M: int = 256, hidden: int = 8192, iters: int = 20):
     """The peer-to-peer all-reduce on the configs[3] message ([256, 8192] bf16 = 4 MiB) and on a
-    decode-sized one ([16, 8192] = 256 KiB) next to RCCL, across the ranks of `dist` (bench.py --gpus N;
+    decode-sized one ([16, 8192] = 256 KiB) next to RCCL, across the ranks of `dist` (bench.py --gpus N --full;
     VLLM_AMD_BENCH_CUSTOM_AR=0 skips it).  This path has never run across GPUs, so every step is guarded:
     a 2 s barrier time limit, the result is checked against RCCL's BEFORE anything is timed, and the leg
     stops at the first time-out or mismatch (all ranks agree on that through an RCCL reduction).  The IPC
