@@ -188,6 +188,22 @@ int vllm_amd_dynamic_per_token_scaled_fp8_quant(void* out, const void* input,
                                                 int64_t num_tokens,
                                                 int hidden_size, int dtype,
                                                 void* stream);
+/* Replaces torch.ops._C.per_token_group_fp8_quant (the activation quantiser of block-scaled
+ * fp8 linear layers)
+ *   schema csrc/torch_bindings.cpp:623-627, csrc/quantization/fp8/per_token_group_quant.cu:27-119.
+ * For every group of group_size consecutive elements of a row:
+ *   s = max(eps, max|x|) / fp8_max  (scale_ue8m0: rounded up to a power of two, exactly),
+ *   q = e4m3(clamp(x / s, fp8_min, fp8_max)).
+ * out_q: e4m3 [num_tokens, hidden] contiguous; out_s: float, element (token, group) at
+ * out_s[token * s_stride_token + group * s_stride_group] -- row-major [T, H/g] and the
+ * reference's token-contiguous ("column-major") layout are both a pair of strides.
+ * hidden_size % group_size == 0; group_size a multiple of 8, at most 512; input 16-byte and
+ * out_q 8-byte aligned. */
+int vllm_amd_per_token_group_fp8_quant(void* out_q, float* out_s, const void* input,
+                                       int64_t num_tokens, int hidden_size, int group_size,
+                                       float eps, float fp8_min, float fp8_max,
+                                       int scale_ue8m0, int64_t s_stride_token,
+                                       int64_t s_stride_group, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* w8a8 fp8 GEMMs                                                             */
@@ -207,6 +223,24 @@ int vllm_amd_scaled_mm(void* out, const void* a, const void* b,
                        const void* bias, int M, int N, int K, int64_t lda,
                        int64_t ldb, int64_t ldc, int a_scale_numel,
                        int b_scale_numel, int out_dtype, void* stream);
+
+/* The blockwise form of torch.ops._C.cutlass_scaled_mm ("blockwise scaling like found in
+ * DeepSeek V3", python vllm/_custom_ops.py:709-723): 1 x 128 activation scales, 128 x 128
+ * weight scales, applied inside the K loop.
+ * out[m,n] = (sum_kb a_scales[m,kb] * b_scales[kb,n/128] * sum_{k in block kb} a[m,k] b[k,n])
+ *            .to(out_dtype) (+ bias[n])
+ * a, b, bias, out, lda, ldb, ldc as for vllm_amd_scaled_mm.
+ * a_scales: float [M, K/128], element (m,kb) at a_scales[m*as_stride_m + kb*as_stride_k]
+ * (row-major or token-contiguous, read in place); b_scales: float [K/128, ceil(N/128)],
+ * element (kb,nb) at b_scales[kb*bs_stride_k + nb*bs_stride_n] (a checkpoint's
+ * [N/128, K/128] tensor is this with the strides swapped).  K % 128 == 0 (else
+ * VLLM_AMD_EUNSUPPORTED), N arbitrary; lda, ldb >= K and multiples of 16.  No workspace. */
+int vllm_amd_scaled_mm_blockwise(void* out, const void* a, const void* b,
+                                 const float* a_scales, const float* b_scales,
+                                 const void* bias, int M, int N, int K, int64_t lda,
+                                 int64_t ldb, int64_t ldc, int64_t as_stride_m,
+                                 int64_t as_stride_k, int64_t bs_stride_k,
+                                 int64_t bs_stride_n, int out_dtype, void* stream);
 
 /* No counterpart in the reference (its libraries own their workspaces): registers (ws != NULL)
  * or removes (ws == NULL) the CURRENT device's workspace -- `bytes` of caller-owned device
@@ -507,6 +541,9 @@ int vllm_amd_ar_free_shared(void* ptr);
 /*                 (0 = heuristic, 1 = never split, n = n slices; reduced       */
 /*                 inside the kernel through the registered workspace,          */
 /*                 vllm_amd_set_workspace; unsplit without one)                 */
+/*   "mm_block_kernel": form of scaled_mm_blockwise: 0 = by M (streaming kernel */
+/*                 up to M 64, tile kernel above), 1 = tile kernel always,      */
+/*                 2 / 3 = its 128-row / 256-row form always                    */
 /* ------------------------------------------------------------------------- */
 int vllm_amd_set_tuning(const char* key, int value);
 /* current value of "pa_balance" / "mm_kernel" / "mm_splitk" (the torch layer asks before it allocates) */

@@ -181,13 +181,30 @@ def scaled_fp8_quant(
     return output, scale
 
 
+# csrc/torch_bindings.cpp:623-627 (the reference calls the op directly from fp8_utils.py)
+def per_token_group_fp8_quant(input: torch.Tensor, output_q: torch.Tensor, output_s: torch.Tensor,
+                              group_size: int, eps: float, fp8_min: float, fp8_max: float,
+                              scale_ue8m0: bool) -> None:
+    """Quantize every ``group_size`` consecutive elements of a row with a scale of their own;
+    writes ``output_q`` (fp8, contiguous) and ``output_s`` (fp32 [tokens, hidden / group_size],
+    any strides)."""
+    torch.ops._C.per_token_group_fp8_quant(input, output_q, output_s, group_size, eps, fp8_min,
+                                           fp8_max, scale_ue8m0)
+
+
 # vllm/_custom_ops.py:697-742
 def cutlass_scaled_mm(a: torch.Tensor, b: torch.Tensor, scale_a: torch.Tensor,
                       scale_b: torch.Tensor, out_dtype: torch.dtype,
                       bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """output = torch.mm((scale_a * a), (scale_b * b)).to(out_dtype) (+ bias), with
     scale_a per-tensor [1] or per-token [M,1], scale_b per-tensor or per-channel [N,1].
-    a: fp8 [M,K] row-major; b: fp8 [K,N] column-major (``weight.t()``)."""
+    a: fp8 [M,K] row-major; b: fp8 [K,N] column-major (``weight.t()``).
+
+    Group broadcast (blockwise scaling as in DeepSeek V3): 2-D scales with
+    ``scale_a.shape * [1, 128] == a.shape`` and ``scale_b.shape * [128, 128] == b.shape``
+    (the last block of N may be ragged), fp32, any strides: every 128-wide slice of the
+    reduction is weighted by ``scale_a[m, k // 128] * scale_b[k // 128, n // 128]``.
+    K must be a multiple of 128."""
     assert out_dtype is torch.bfloat16 or out_dtype is torch.float16
     assert bias is None or (bias.shape[0] == b.shape[1] and bias.dtype == out_dtype)
     m, n = a.shape[0], b.shape[1]

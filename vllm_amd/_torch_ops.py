@@ -102,6 +102,7 @@ swap_blocks = torch.ops._C_cache_ops.swap_blocks
 static_scaled_fp8_quant = torch.ops._C.static_scaled_fp8_quant
 dynamic_scaled_fp8_quant = torch.ops._C.dynamic_scaled_fp8_quant
 dynamic_per_token_scaled_fp8_quant = torch.ops._C.dynamic_per_token_scaled_fp8_quant
+per_token_group_fp8_quant = torch.ops._C.per_token_group_fp8_quant
 cutlass_scaled_mm = torch.ops._C.cutlass_scaled_mm
 wvSplitKQ = torch.ops._rocm_C.wvSplitKQ
 rms_norm_static_fp8_quant = torch.ops._C.rms_norm_static_fp8_quant

@@ -25,6 +25,7 @@
 namespace va {
 
 extern int g_mm_kernel;
+extern int g_mm_block_kernel;   // scaled_mm_block.hip
 extern int g_mm_splitk;
 extern int g_mm_tail;
 extern int g_mm_patch;
@@ -580,6 +581,7 @@ extern "C" int vllm_amd_set_tuning(const char* key, int value) {
   if (strcmp(key, "uni_hp") == 0) { g_uni_hp = value; return VLLM_AMD_OK; }
   if (strcmp(key, "mm_splitk") == 0) { g_mm_splitk = value; return VLLM_AMD_OK; }
   if (strcmp(key, "mm_tail") == 0) { g_mm_tail = value; return VLLM_AMD_OK; }
+  if (strcmp(key, "mm_block_kernel") == 0) { g_mm_block_kernel = value; return VLLM_AMD_OK; }
   if (strcmp(key, "mm_patch") == 0) { g_mm_patch = value; return VLLM_AMD_OK; }
   if (strcmp(key, "mm_store") == 0) { g_mm_store = value; return VLLM_AMD_OK; }
   if (strcmp(key, "mm_prio") == 0) { g_mm_prio = value; return VLLM_AMD_OK; }

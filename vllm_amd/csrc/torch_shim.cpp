@@ -292,6 +292,27 @@ void dynamic_per_token_scaled_fp8_quant(Tensor& result, const Tensor& input, Ten
                                                     stream_of(input)));
 }
 
+// csrc/quantization/fp8/per_token_group_quant.cu:121-217
+void per_token_group_fp8_quant(const Tensor& input, Tensor& output_q, Tensor& output_s, int64_t group_size, double eps,
+                               double fp8_min, double fp8_max, bool scale_ue8m0) {
+  need_devs(input, output_q, output_s);
+  TORCH_CHECK(input.is_contiguous(), "input.is_contiguous()");
+  TORCH_CHECK(output_q.is_contiguous(), "output_q.is_contiguous()");
+  TORCH_CHECK(is_fp8(output_q), "Unsupported fp8 type: ", output_q.scalar_type());
+  TORCH_CHECK(group_size > 0 && input.dim() >= 1 && input.size(-1) % group_size == 0 &&
+                  output_q.numel() == input.numel(),
+              "input.numel() % group_size == 0");
+  const int64_t hidden = input.size(-1), nt = rows_of(input, hidden), groups = hidden / group_size;
+  TORCH_CHECK(output_s.dim() == 2 && output_s.scalar_type() == at::kFloat && output_s.size(0) == nt &&
+                  output_s.size(1) == groups,
+              "output_s.dim() == 2 (float32 [num_tokens, hidden / group_size])");
+  DevGuard g(input.device());
+  check(vllm_amd_per_token_group_fp8_quant(output_q.data_ptr(), (float*)output_s.data_ptr(), input.data_ptr(), nt,
+                                           (int)hidden, (int)group_size, (float)eps, (float)fp8_min, (float)fp8_max,
+                                           scale_ue8m0 ? 1 : 0, output_s.stride(0), output_s.stride(1), dt(input),
+                                           stream_of(input)));
+}
+
 // ---- GEMM --------------------------------------------------------------------------------
 // csrc/quantization/cutlass_w8a8/scaled_mm_entry.cu checks, restated
 void cutlass_scaled_mm(Tensor& out, const Tensor& a, const Tensor& b, const Tensor& a_scales,
@@ -307,12 +328,29 @@ void cutlass_scaled_mm(Tensor& out, const Tensor& a, const Tensor& b, const Tens
   TORCH_CHECK(is_fp8(a) && is_fp8(b), "scaled_mm: only fp8 e4m3 x fp8 e4m3 is implemented on gfx950");
   TORCH_CHECK(a_scales.scalar_type() == at::kFloat && b_scales.scalar_type() == at::kFloat,
               "scales must be float32");
-  TORCH_CHECK(a_scales.is_contiguous() && b_scales.is_contiguous(),
-              "a_scales.is_contiguous() && b_scales.is_contiguous()");
   TORCH_CHECK(!bias.has_value() || (bias->numel() == N && bias->is_contiguous() && bias->dim() == 1 &&
                                     bias->scalar_type() == out.scalar_type()),
               "bias.numel() == b.size(1) && bias.is_contiguous() && bias.dim() == 1");
   DevGuard g(a.device());
+  // per-tensor / per-token / per-channel scales first; the only shapes that are also group scales have
+  // K = 128, where both rules mean the same product
+  const bool plain = (a_scales.numel() == 1 || a_scales.numel() == M) && (b_scales.numel() == 1 || b_scales.numel() == N);
+  if (!plain) {
+    // group broadcast (vllm/_custom_ops.py:709-723): a_scales [M, K/128], b_scales [K/128, ceil(N/128)], any strides
+    const int64_t kb = K / 128, nb = (N + 127) / 128;
+    TORCH_CHECK(K % 128 == 0 && a_scales.dim() == 2 && b_scales.dim() == 2 && a_scales.size(0) == M &&
+                    a_scales.size(1) == kb && b_scales.size(0) == kb && b_scales.size(1) == nb,
+                "cutlass_scaled_mm: scales must be per-tensor ([1]), per-token / per-channel (a_scales [M, 1], "
+                "b_scales [N, 1]), or blockwise (a_scales [M, K/128], b_scales [K/128, ceil(N/128)]); got a_scales ",
+                a_scales.sizes(), ", b_scales ", b_scales.sizes(), " for M, N, K = ", M, ", ", N, ", ", K);
+    check(vllm_amd_scaled_mm_blockwise(out.data_ptr(), a.data_ptr(), b.data_ptr(), fptr(a_scales), fptr(b_scales),
+                                       vptr(bias), (int)M, (int)N, (int)K, a.stride(0), b.stride(1), out.stride(0),
+                                       a_scales.stride(0), a_scales.stride(1), b_scales.stride(0), b_scales.stride(1),
+                                       dt(out), stream_of(a)));
+    return;
+  }
+  TORCH_CHECK(a_scales.is_contiguous() && b_scales.is_contiguous(),
+              "a_scales.is_contiguous() && b_scales.is_contiguous()");
   check(vllm_amd_scaled_mm(out.data_ptr(), a.data_ptr(), b.data_ptr(), fptr(a_scales), fptr(b_scales), vptr(bias),
                            (int)M, (int)N, (int)K, a.stride(0), b.stride(1), out.stride(0), (int)a_scales.numel(),
                            (int)b_scales.numel(), dt(out), stream_of(a)));
@@ -474,6 +512,10 @@ void register_all() {
        "dynamic_per_token_scaled_fp8_quant(Tensor! result, Tensor input, Tensor! scale,"
        " Tensor? scale_ub) -> ()",
        &dynamic_per_token_scaled_fp8_quant);
+  c.op("per_token_group_fp8_quant",
+       "per_token_group_fp8_quant(Tensor input, Tensor! output_q, Tensor! output_s, "
+       "int group_size, float eps, float fp8_min, float fp8_max, bool scale_ue8m0) -> ()",
+       &per_token_group_fp8_quant);
   c.op("cutlass_scaled_mm",
        "cutlass_scaled_mm(Tensor! out, Tensor a, Tensor b, Tensor a_scales, Tensor b_scales,"
        " Tensor? bias) -> ()",
