@@ -164,6 +164,41 @@ int vllm_amd_copy_blocks(void* key_cache, void* value_cache,
                          const int64_t* block_mapping, int num_pairs,
                          int64_t block_bytes, void* stream);
 
+/* Replaces torch.ops._C_cache_ops.concat_and_cache_mla
+ *   schema csrc/torch_bindings.cpp (cache_ops, "concat_and_cache_mla"), csrc/cache_kernels.cu:309-350,
+ *   465-501, python vllm/_custom_ops.py:1648-1658.
+ * kv_c [>= num_tokens, kv_lora_rank], k_pe [>= num_tokens, pe_dim] (row strides kv_c_stride /
+ * k_pe_stride), kv_cache [num_blocks, block_size, kv_lora_rank + pe_dim] addressed through
+ * block_stride / entry_stride; num_tokens = slot_mapping.size(0), slots < 0 are skipped.
+ * kv_dtype AUTO: a bit copy (float16 / bfloat16); FP8_E4M3: a byte cache, x / *scale as in
+ * reshape_and_cache_flash (scale: device float[1]). */
+int vllm_amd_concat_and_cache_mla(
+    const void* kv_c, const void* k_pe, void* kv_cache, const int64_t* slot_mapping,
+    int num_tokens, int kv_lora_rank, int pe_dim, int block_size, int64_t kv_c_stride,
+    int64_t k_pe_stride, int64_t block_stride, int64_t entry_stride, int dtype,
+    int kv_dtype, const float* scale, void* stream);
+
+/* Multi-head latent attention decode over the cache written by concat_and_cache_mla: replaces the
+ * Triton path decode_attention_fwd (vllm/attention/ops/triton_decode_attention.py:629-674, kernels
+ * :228-378 and :471-525) as TritonMLAImpl._forward_decode calls it
+ * (vllm/v1/attention/backends/mla/triton_mla.py:124-171).
+ * q [batch, num_heads, 576], o [batch, num_heads, 512] (dtype: float16 / bfloat16, last dimension
+ * contiguous), kv_cache [num_blocks, page_size, 576] of the same type (cache_dtype; kv_dtype must be
+ * AUTO), v = the rows' first 512 columns; block_table int32 [batch, max_blocks_per_seq] (row stride
+ * block_table_stride), seq_lens int32 [batch] (index_bits = 32; anything else is refused);
+ * attn_logits: the caller's float scratch of attn_logits_floats >= batch * num_heads *
+ * num_kv_splits * 513 floats, 16-byte aligned (unused when num_kv_splits == 1).  Split s covers
+ * tokens [s L, min((s + 1) L, len)), L = ceil(len / num_kv_splits).  A sequence of length 0 gets
+ * a zero row (the reference computes 0 / 0).  logit_cap is not supported. */
+int vllm_amd_mla_decode(
+    void* o, const void* q, const void* kv_cache, const void* block_table,
+    const void* seq_lens, float* attn_logits, int64_t attn_logits_floats, int batch,
+    int num_heads, int qk_width, int v_width, int page_size, int max_blocks_per_seq,
+    int num_kv_splits, float sm_scale, int64_t q_stride_b, int64_t q_stride_h,
+    int64_t o_stride_b, int64_t o_stride_h, int64_t cache_block_stride,
+    int64_t cache_entry_stride, int64_t block_table_stride, int dtype, int cache_dtype,
+    int kv_dtype, int index_bits, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* fp8 (e4m3fn) quantisation, input [num_tokens, hidden] contiguous           */
 /* ------------------------------------------------------------------------- */

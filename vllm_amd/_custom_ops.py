@@ -124,6 +124,14 @@ def reshape_and_cache_flash(key, value, key_cache, value_cache, slot_mapping,
                                                    slot_mapping, kv_cache_dtype, k_scale, v_scale)
 
 
+# vllm/_custom_ops.py:1648-1658
+def concat_and_cache_mla(kv_c: torch.Tensor, k_pe: torch.Tensor, kv_cache: torch.Tensor,
+                         slot_mapping: torch.Tensor, kv_cache_dtype: str,
+                         scale: torch.Tensor) -> None:
+    torch.ops._C_cache_ops.concat_and_cache_mla(kv_c, k_pe, kv_cache, slot_mapping,
+                                                kv_cache_dtype, scale)
+
+
 # vllm/_custom_ops.py:1661-1664
 def copy_blocks(key_caches: list[torch.Tensor], value_caches: list[torch.Tensor],
                 block_mapping: torch.Tensor) -> None:

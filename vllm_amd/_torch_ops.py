@@ -96,6 +96,7 @@ paged_attention_v2 = torch.ops._C.paged_attention_v2
 paged_attention_rocm = torch.ops._rocm_C.paged_attention
 reshape_and_cache = torch.ops._C_cache_ops.reshape_and_cache
 reshape_and_cache_flash = torch.ops._C_cache_ops.reshape_and_cache_flash
+concat_and_cache_mla = torch.ops._C_cache_ops.concat_and_cache_mla
 convert_fp8 = torch.ops._C_cache_ops.convert_fp8
 copy_blocks = torch.ops._C_cache_ops.copy_blocks
 swap_blocks = torch.ops._C_cache_ops.swap_blocks

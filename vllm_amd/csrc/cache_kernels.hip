@@ -584,3 +584,129 @@ extern "C" int vllm_amd_copy_blocks(void* key_cache, void* value_cache,
   VA_LAUNCH_CHECK("copy_blocks launch");
   return VLLM_AMD_OK;
 }
+
+// ---------------------------------------------------------------------------
+// concat_and_cache_mla: kv_cache[slot / bs, slot % bs, :] = [kv_c[i] | k_pe[i]] (csrc/cache_kernels.cu:309-350,
+// 465-501).  A bandwidth kernel: a workgroup of 256 threads takes 8 tokens; an item is one 16-byte source
+// vector (8 elements) of one token's row, (512 + 64) / 8 = 72 per token, so the usual row is 576 items = 3
+// rounds of the workgroup, and ALL loads of a batch of 3 rounds are issued before its first store.  The
+// destination is a 16-byte ("auto": a bit copy) or 8-byte (fp8: kv_quant_vec, the arithmetic of
+// reshape_and_cache_flash / convert_fp8) vector.  Wider rows take more batches; widths or strides that are
+// no multiple of 8, or misaligned pointers, take the element kernel below.
+// ---------------------------------------------------------------------------
+namespace va {
+constexpr int MLA_CW_TOK = 8, MLA_CW_IT = 3;
+
+template <typename scalar_t, typename cache_t, bool FP8>
+__global__ __launch_bounds__(256) void concat_and_cache_mla_kernel(
+    const scalar_t* __restrict__ kv_c, const scalar_t* __restrict__ k_pe, cache_t* __restrict__ kv_cache,
+    const int64_t* __restrict__ slot_mapping, int num_tokens, int rank_chunks, int row_chunks, int block_size,
+    int64_t kv_c_stride, int64_t k_pe_stride, int64_t block_stride, int64_t entry_stride,
+    const float* __restrict__ scale_p) {
+  const int t0 = blockIdx.x * MLA_CW_TOK;
+  const int n = min(MLA_CW_TOK, num_tokens - t0);
+  const int items = n * row_chunks;
+  Divisor sc(1.f);
+  if constexpr (FP8) sc = Divisor(*scale_p);
+  for (int base = 0; base < items; base += MLA_CW_IT * 256) {
+    Vec<scalar_t, 8> v[MLA_CW_IT];
+    int64_t dst[MLA_CW_IT];
+#pragma unroll
+    for (int u = 0; u < MLA_CW_IT; ++u) {
+      const int it = base + u * 256 + threadIdx.x;
+      dst[u] = -1;
+      if (it >= items) continue;
+      const int i = it / row_chunks, c = it - i * row_chunks;
+      const int64_t slot = slot_mapping[t0 + i];
+      if (slot < 0) continue;   // padded token
+      const scalar_t* src = c < rank_chunks ? kv_c + (int64_t)(t0 + i) * kv_c_stride + c * 8
+                                            : k_pe + (int64_t)(t0 + i) * k_pe_stride + (c - rank_chunks) * 8;
+      v[u] = *reinterpret_cast<const Vec<scalar_t, 8>*>(src);
+      dst[u] = slot / block_size * block_stride + slot % block_size * entry_stride + c * 8;
+    }
+#pragma unroll
+    for (int u = 0; u < MLA_CW_IT; ++u) {
+      if (dst[u] < 0) continue;
+      if constexpr (FP8) {
+        Vec<uint8_t, 8> qv;
+        kv_quant_vec(v[u], sc, qv);
+        *reinterpret_cast<Vec<uint8_t, 8>*>(kv_cache + dst[u]) = qv;
+      } else {
+        *reinterpret_cast<Vec<scalar_t, 8>*>(kv_cache + dst[u]) = v[u];
+      }
+    }
+  }
+}
+
+// any widths, strides and alignments: one workgroup per token, one element per thread and step
+template <typename scalar_t, typename cache_t, bool FP8>
+__global__ void concat_and_cache_mla_scalar_kernel(
+    const scalar_t* __restrict__ kv_c, const scalar_t* __restrict__ k_pe, cache_t* __restrict__ kv_cache,
+    const int64_t* __restrict__ slot_mapping, int kv_lora_rank, int pe_dim, int block_size, int64_t kv_c_stride,
+    int64_t k_pe_stride, int64_t block_stride, int64_t entry_stride, const float* __restrict__ scale_p) {
+  const int64_t token = blockIdx.x;
+  const int64_t slot = slot_mapping[token];
+  if (slot < 0) return;
+  cache_t* dst = kv_cache + slot / block_size * block_stride + slot % block_size * entry_stride;
+  Divisor sc(1.f);
+  if constexpr (FP8) sc = Divisor(*scale_p);
+  for (int i = threadIdx.x; i < kv_lora_rank + pe_dim; i += blockDim.x) {
+    const scalar_t x = i < kv_lora_rank ? kv_c[token * kv_c_stride + i] : k_pe[token * k_pe_stride + i - kv_lora_rank];
+    if constexpr (FP8) dst[i] = f32_to_fp8(kv_quant_prep(x, sc));
+    else dst[i] = x;
+  }
+}
+}  // namespace va
+
+template <typename scalar_t, bool FP8>
+static int launch_concat_mla(const void* kv_c, const void* k_pe, void* cache, const int64_t* slot_mapping,
+                             int num_tokens, int rank, int pe, int block_size, int64_t kv_c_stride,
+                             int64_t k_pe_stride, int64_t block_stride, int64_t entry_stride, const float* scale,
+                             hipStream_t st) {
+  typedef typename std::conditional<FP8, uint8_t, scalar_t>::type cache_t;
+  const bool vec_ok = rank % 8 == 0 && pe % 8 == 0 && kv_c_stride % 8 == 0 && k_pe_stride % 8 == 0 &&
+                      block_stride % 8 == 0 && entry_stride % 8 == 0 && aligned(kv_c, 16) && aligned(k_pe, 16) &&
+                      aligned(cache, 8 * sizeof(cache_t));
+  if (vec_ok) {
+    hipLaunchKernelGGL((concat_and_cache_mla_kernel<scalar_t, cache_t, FP8>), dim3(ceil_div(num_tokens, MLA_CW_TOK)),
+                       dim3(256), 0, st, (const scalar_t*)kv_c, (const scalar_t*)k_pe, (cache_t*)cache, slot_mapping,
+                       num_tokens, rank / 8, (rank + pe) / 8, block_size, kv_c_stride, k_pe_stride, block_stride,
+                       entry_stride, scale);
+  } else {
+    hipLaunchKernelGGL((concat_and_cache_mla_scalar_kernel<scalar_t, cache_t, FP8>), dim3(num_tokens), dim3(256), 0,
+                       st, (const scalar_t*)kv_c, (const scalar_t*)k_pe, (cache_t*)cache, slot_mapping, rank, pe,
+                       block_size, kv_c_stride, k_pe_stride, block_stride, entry_stride, scale);
+  }
+  VA_LAUNCH_CHECK("concat_and_cache_mla launch");
+  return VLLM_AMD_OK;
+}
+
+extern "C" int vllm_amd_concat_and_cache_mla(const void* kv_c, const void* k_pe, void* kv_cache,
+                                             const int64_t* slot_mapping, int num_tokens, int kv_lora_rank,
+                                             int pe_dim, int block_size, int64_t kv_c_stride, int64_t k_pe_stride,
+                                             int64_t block_stride, int64_t entry_stride, int dtype, int kv_dtype,
+                                             const float* scale, void* stream) {
+  VA_REQUIRE(num_tokens >= 0 && kv_lora_rank > 0 && pe_dim >= 0 && block_size > 0, VLLM_AMD_EINVAL,
+             "concat_and_cache_mla: bad shape");
+  VA_REQUIRE(entry_stride >= kv_lora_rank + pe_dim, VLLM_AMD_EINVAL,
+             "concat_and_cache_mla: cache entry stride %lld < kv_lora_rank + pe_dim = %d", (long long)entry_stride,
+             kv_lora_rank + pe_dim);
+  VA_REQUIRE(dtype == VLLM_AMD_F16 || dtype == VLLM_AMD_BF16, VLLM_AMD_EUNSUPPORTED,
+             "Unsupported input type of kv cache: %d", dtype);
+  VA_REQUIRE(kv_dtype == VLLM_AMD_KV_AUTO || kv_dtype == VLLM_AMD_KV_FP8_E4M3, VLLM_AMD_EUNSUPPORTED,
+             "Unsupported data type of kv cache: %d", kv_dtype);
+  if (num_tokens == 0) return VLLM_AMD_OK;
+  VA_REQUIRE(kv_c && k_pe && kv_cache && slot_mapping && (kv_dtype == VLLM_AMD_KV_AUTO || scale), VLLM_AMD_EINVAL,
+             "concat_and_cache_mla: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+#define CM(T, F)                                                                                              \
+  return launch_concat_mla<T, F>(kv_c, k_pe, kv_cache, slot_mapping, num_tokens, kv_lora_rank, pe_dim,         \
+                                 block_size, kv_c_stride, k_pe_stride, block_stride, entry_stride, scale, st)
+  if (kv_dtype == VLLM_AMD_KV_AUTO) {
+    if (dtype == VLLM_AMD_F16) CM(f16_t, false);
+    CM(bf16_t, false);
+  }
+  if (dtype == VLLM_AMD_F16) CM(f16_t, true);
+  CM(bf16_t, true);
+#undef CM
+}

@@ -1,0 +1,540 @@
+// Multi-head latent attention (MLA) decode over the latent KV cache, for gfx950.
+//
+//   cache  [num_blocks, page_size, 576]   one row per token: 512 latent columns (kv_c), then 64
+//                                         rotary columns (k_pe); shared by every query head
+//   q      [B, H, 576]                    o [B, H, 512]
+//   logits = sm_scale * q . row (all 576 columns), softmax over the sequence's tokens, o = sum p * row[0:512]
+//
+// Semantics: _fwd_grouped_kernel_stage1 + _fwd_kernel_stage2 of the reference's
+// vllm/attention/ops/triton_decode_attention.py:228-378, 471-525 as the MLA backend calls them
+// (vllm/v1/attention/backends/mla/triton_mla.py:124-171): fp32 online softmax, the probabilities rounded
+// to the data type before PV (their sum is taken before the rounding, as there), split s of a sequence
+// covers tokens [s L, min((s + 1) L, len)) with L = ceil(len / num_kv_splits), empty splits write and
+// read nothing, partials are merged by log-sum-exp.  DEVIATION: a sequence of length 0 gets a ZERO output
+// row; the reference computes 0 / 0 there.  logit_cap and an fp8 cache are not supported (the reference's
+// MLA backend rejects both, triton_mla.py:55-59, 134-135).
+//
+// Work split.  One workgroup (8 waves) = one (sequence, split, chunk of 16 G heads), G = 1 or 2
+// ("heads per workgroup" 16 / 32, chosen by the launcher, tuning key "mla_hpw").  G = 4 is written (the
+// template covers it) but not instantiated: as compiled it needs about 270 of the 256 registers a wave
+// of an 8-wave workgroup has and spills four q fragments.  The workgroup walks its tokens in tiles of
+// T = 32:
+//   * rows -> LDS: global_load_lds, 16 B per lane, straight from the paged cache (gather granularity =
+//     one token, any page size) into a ring of 3 stages, two tiles in flight under the current tile's
+//     math.  A row is fetched ONCE per workgroup and serves both products from LDS.  The LDS image pads a
+//     row to 73 chunks of 16 B (1168 B = 292 words, 36 mod 64 banks): 16 consecutive rows then start in 16
+//     different 4-bank groups, which makes the K-operand reads (16 rows x 16 B per pass) conflict-free,
+//     and rows r .. r + 3 are 36 words apart, which does the same for the V-operand reads below.
+//   * S = K q^T: mfma_f32_16x16x32, A = 16 token rows x 32 columns (one ds_read_b128 per lane), B = q
+//     (16 heads), 18 steps over the 576 columns.  The 2 G (token subtile, head group) items go to waves
+//     0 .. 2 G - 1; a wave keeps the q fragments of its group in 72 registers for the whole split.
+//     Result: lane (c16, g4) holds tokens 4 g4 .. + 3 of head c16.
+//   * softmax: per-wave row maxima and sums meet in LDS (two barriers per tile); every wave tracks the
+//     running maximum and sum of all 16 G heads (lane c16 <-> head c16 of each group), so no wave waits
+//     for another one's rescale factor.  P is rounded to the data type and written to LDS.
+//   * O^T += V^T P^T: the 16 x 512 output of a head group is divided by V column: wave w owns columns
+//     [64 w, 64 w + 64) of ALL G groups (16 G accumulator registers).  A = V^T: lane (c16, g4) needs
+//     column c16 of 8 tokens, i.e. the token index is the contraction index.  It is read with 8
+//     ds_read_u16 per fragment (+ 4 shift-or) -- a transposing read by hand: contraction slot (g4, i) is token
+//     4 i + g4, so one read instruction touches rows i*4 .. i*4 + 3 (36 words apart) x 16 consecutive
+//     16-bit columns (8 words): 32 distinct banks.  P is stored in that slot order ([head][g4][i], rows of
+//     80 B), so its fragment is one ds_read_b128.  Each V fragment is used by G MFMAs.
+//   * every LDS access of the loop is inline assembly: hipcc orders a C++ LDS access behind ALL
+//     outstanding LDS-DMA, which would drain the ring every tile.  The waits are: lgkmcnt(0) inside each
+//     read block / in front of each barrier, and one counted vmcnt in front of the tile's first barrier.
+//     Per tile a lane issues 5 block-table loads (for tile t + 3) and THEN its 5 LDS-DMA (tile t + 2),
+//     so "at most 5 outstanding" = only the youngest tile's DMA is still in flight = tile t has landed.
+//     The block-table entries are loaded one tile before their DMA so that their use does not wait for
+//     the younger DMA in front of them (as compiled, the compiler's own wait at two of those uses per
+//     pair of tiles is still vmcnt(0): DESIGN.md, open items).
+//   * num_kv_splits == 1 writes o directly; otherwise the normalised partial row and the split's
+//     log-sum-exp go to the caller's attn_logits ([B, H, splits, 512] rows, then [B, H, splits] lse: the
+//     tensor's 513 floats per split, regrouped so that rows stay 16-byte aligned) and mla_merge_kernel
+//     combines the non-empty splits.
+// H = 128 runs as four chunks of 32 heads: the later chunks' rows are meant to come from L2 (chunks of
+// one (sequence, split) sit next to each other on the same XCD), so that HBM sees each row once per
+// (sequence, split).
+//
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): see DESIGN.md.
+// Nothing is allocated or synchronised and there is no workspace beyond attn_logits: graph-capturable.
+#include "mma.cuh"
+
+namespace va {
+
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+
+constexpr int MLA_DK = 576, MLA_DV = 512;
+constexpr int MLA_T = 32;                           // tokens per tile
+constexpr int MLA_NW = 8, MLA_NT = MLA_NW * 64;     // waves, threads
+constexpr int MLA_CH = 73;                          // 16-byte chunks per LDS row (72 + 1 pad)
+constexpr int MLA_ROWB = MLA_CH * 16;               // 1168
+constexpr int MLA_PER = 5;                          // LDS-DMA per lane and stage: 5 * 512 >= 32 * 73
+constexpr int MLA_STAGE = MLA_PER * MLA_NT * 16;    // 40960
+constexpr int MLA_NST = 3;
+constexpr int MLA_PROW = 80, MLA_PGRP = 16 * MLA_PROW;   // P: [group][head][32 slots], rows padded to 80 B
+static_assert(MLA_PER * MLA_NT >= MLA_T * MLA_CH, "a stage holds a tile");
+
+int g_mla_hpw = 0;   // tuning "mla_hpw": 0 = by H, 16 / 32 = heads per workgroup
+
+// ---- LDS access of the main loop (see the header) -------------------------------------------------
+template <int OFF>
+__device__ __forceinline__ void lds_read3(uint32_t addr, i32x4 (&v)[3]) {
+  asm volatile(
+      "ds_read_b128 %0, %3 offset:%4\n\tds_read_b128 %1, %3 offset:%5\n\tds_read_b128 %2, %3 offset:%6\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2])
+      : "v"(addr), "n"(OFF), "n"(OFF + 64), "n"(OFF + 128)
+      : "memory");
+}
+// N floats, 64 bytes apart
+template <int N>
+__device__ __forceinline__ void lds_read_f32(uint32_t addr, float (&v)[N]) {
+  static_assert(N == 2 || N == 4 || N == 8, "");
+  if constexpr (N == 2) {
+    asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:64\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(v[0]), "=&v"(v[1]) : "v"(addr) : "memory");
+  } else if constexpr (N == 4) {
+    asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:64\n\tds_read_b32 %2, %4 offset:128\n\t"
+                 "ds_read_b32 %3, %4 offset:192\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]) : "v"(addr) : "memory");
+  } else {
+    asm volatile("ds_read_b32 %0, %8\n\tds_read_b32 %1, %8 offset:64\n\tds_read_b32 %2, %8 offset:128\n\t"
+                 "ds_read_b32 %3, %8 offset:192\n\tds_read_b32 %4, %8 offset:256\n\tds_read_b32 %5, %8 offset:320\n\t"
+                 "ds_read_b32 %6, %8 offset:384\n\tds_read_b32 %7, %8 offset:448\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]),
+                   "=&v"(v[7])
+                 : "v"(addr) : "memory");
+  }
+}
+// the V^T fragment of 16 columns: the 16-bit elements (row 4 i + g4, column c16), i = 0 .. 7; the lane's
+// address already holds g4 and c16, OFF the column tile.  Eight zero-extending 16-bit reads, paired by
+// four shift-or instructions (the d16 forms that would write register halves directly do not keep the
+// other half on this chip: with SRAM ECC they clear it).
+template <int OFF>
+__device__ __forceinline__ i32x4 lds_read_vt(uint32_t addr) {
+  constexpr int R4 = 4 * MLA_ROWB;
+  uint32_t e[8];
+  asm volatile(
+      "ds_read_u16 %0, %8 offset:%9\n\tds_read_u16 %1, %8 offset:%10\n\t"
+      "ds_read_u16 %2, %8 offset:%11\n\tds_read_u16 %3, %8 offset:%12\n\t"
+      "ds_read_u16 %4, %8 offset:%13\n\tds_read_u16 %5, %8 offset:%14\n\t"
+      "ds_read_u16 %6, %8 offset:%15\n\tds_read_u16 %7, %8 offset:%16\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(e[0]), "=&v"(e[1]), "=&v"(e[2]), "=&v"(e[3]), "=&v"(e[4]), "=&v"(e[5]), "=&v"(e[6]), "=&v"(e[7])
+      : "v"(addr), "n"(OFF), "n"(OFF + R4), "n"(OFF + 2 * R4), "n"(OFF + 3 * R4), "n"(OFF + 4 * R4),
+        "n"(OFF + 5 * R4), "n"(OFF + 6 * R4), "n"(OFF + 7 * R4)
+      : "memory");
+  return (i32x4){(int)(e[0] | e[1] << 16), (int)(e[2] | e[3] << 16), (int)(e[4] | e[5] << 16),
+                 (int)(e[6] | e[7] << 16)};
+}
+// the P^T fragments of G head groups, MLA_PGRP bytes apart
+template <int G>
+__device__ __forceinline__ void lds_read_p(uint32_t addr, i32x4 (&v)[G]) {
+  static_assert(G == 1 || G == 2 || G == 4, "");
+  if constexpr (G == 1) {
+    asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v[0]) : "v"(addr) : "memory");
+  } else if constexpr (G == 2) {
+    asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:%3\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(v[0]), "=&v"(v[1]) : "v"(addr), "n"(MLA_PGRP) : "memory");
+  } else {
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:%5\n\tds_read_b128 %2, %4 offset:%6\n\t"
+                 "ds_read_b128 %3, %4 offset:%7\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
+                 : "v"(addr), "n"(MLA_PGRP), "n"(2 * MLA_PGRP), "n"(3 * MLA_PGRP) : "memory");
+  }
+}
+__device__ __forceinline__ void lds_write_b32(uint32_t addr, float v) {
+  asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void lds_write_b16(uint32_t addr, uint32_t v) {
+  asm volatile("ds_write_b16 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
+}
+__device__ __forceinline__ void lds_barrier() {   // own LDS traffic done, then everybody's
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+template <typename T> __device__ __forceinline__ uint32_t bits16(T v) {
+  return (uint32_t)__builtin_bit_cast(uint16_t, v);
+}
+
+// ---------------------------------------------------------------------------------------------
+// main kernel
+// ---------------------------------------------------------------------------------------------
+template <typename T, int G>
+__global__ __launch_bounds__(MLA_NT) void mla_decode_kernel(
+    T* __restrict__ o, const T* __restrict__ q, const T* __restrict__ cache, const int* __restrict__ block_table,
+    const int* __restrict__ seq_lens, float* __restrict__ scratch, int B, int H, int S, int NC, int page_size,
+    uint32_t ps_magic, int max_blocks, float scale2, int64_t q_sb, int64_t q_sh, int64_t o_sb, int64_t o_sh,
+    int64_t c_sb, int64_t c_se, int64_t bt_s, int o_vec) {
+  constexpr int NQ = 2 * G;   // waves with a QK item
+  constexpr int P_OFF = MLA_NST * MLA_STAGE, MAX_OFF = P_OFF + G * MLA_PGRP, SUM_OFF = MAX_OFF + MLA_NW * 64;
+  static_assert(SUM_OFF + MLA_NW * 64 <= 160 * 1024, "LDS");
+  __shared__ __attribute__((aligned(16))) uint8_t lds[SUM_OFF + MLA_NW * 64];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c16 = lane & 15, g4 = lane >> 4;
+
+  // hardware workgroup i runs on XCD i % 8: the NC head chunks of one (sequence, split) take
+  // consecutive slots of ONE XCD, so all but the first find the rows in that XCD's L2
+  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+  const int chunk = idx % NC, u = (idx / NC) * 8 + xcd;
+  if (u >= B * S) return;
+  const int b = u / S, split = u - b * S;
+  const int h0 = chunk * 16 * G;
+  const int len = seq_lens[b];
+  if (len <= 0) {
+    if (S == 1)   // the merge kernel writes the zero row otherwise
+      for (int i = tid; i < 16 * G * MLA_DV; i += MLA_NT) {
+        const int h = h0 + i / MLA_DV;
+        if (h < H) o[b * o_sb + h * o_sh + i % MLA_DV] = from_f32<T>(0.f);
+      }
+    return;
+  }
+  const int L = (len + S - 1) / S;
+  const int start = split * L, end = min(start + L, len);
+  if (start >= end) return;
+  const int ntiles = (end - start + MLA_T - 1) / MLA_T;
+
+  const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
+
+  // ---- the row-load path (the one place a converting load would go): LDS position p = 512 r + tid of
+  // a stage is chunk p % 73 of tile row p / 73; pad chunks and positions past the tile re-read chunk 0
+  // (never used).  Rows past the split's end re-read its last token: finite data under a zero weight.
+  int ppos[MLA_PER];   // row | first element << 8
+#pragma unroll
+  for (int r = 0; r < MLA_PER; ++r) {
+    const int p = r * MLA_NT + tid;
+    int row = p / MLA_CH, c = p - row * MLA_CH;
+    if (row >= MLA_T) row = 0, c = 0;
+    if (c == MLA_CH - 1) c = 0;
+    ppos[r] = row | (c * 8) << 8;
+  }
+  const int* bt_row = block_table + b * bt_s;
+  // (the position passes through an empty asm: the 64-bit address parts derived from it would otherwise be
+  // hoisted out of the tile loop, ten registers the 64-head variant does not have)
+  auto locate = [&](int t, int r, int& pos, int& blk, int& within) {
+    pos = ppos[r];
+    asm volatile("" : "+v"(pos));
+    const int tok = min(start + t * MLA_T + (pos & 255), end - 1);
+    // tok / page_size without a branch: ps_magic = floor(2^32 / page_size) (2^32 - 1 for 1) gives the
+    // quotient or one less
+    blk = (int)__umulhi((uint32_t)tok, ps_magic);
+    within = tok - blk * page_size;
+    const bool fix = within >= page_size;
+    blk += fix ? 1 : 0;
+    within -= fix ? page_size : 0;
+  };
+  auto table_load = [&](int t, int (&page)[MLA_PER]) {
+#pragma unroll
+    for (int r = 0; r < MLA_PER; ++r) {
+      int pos, blk, within;
+      locate(t, r, pos, blk, within);
+      page[r] = bt_row[min(blk, max_blocks - 1)];
+    }
+  };
+  auto stage_rows = [&](int t, int stage, const int (&page)[MLA_PER]) {
+    uint8_t* dst = lds + stage * MLA_STAGE + wave * 1024;
+#pragma unroll
+    for (int r = 0; r < MLA_PER; ++r) {
+      int pos, blk, within;
+      locate(t, r, pos, blk, within);
+      const T* src = cache + (int64_t)page[r] * c_sb + (int64_t)within * c_se + (pos >> 8);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                       (__attribute__((address_space(3))) void*)(dst + r * MLA_NT * 16), 16, 0, 0);
+    }
+  };
+
+  // ---- q fragments of this wave's QK item (group gq, token subtile sub), resident for the split
+  const bool qk_wave = wave < NQ;
+  const int gq = wave % G, sub = (wave / G) & 1;
+  i32x4 qf[18];
+  {
+    const int head = h0 + gq * 16 + c16;
+    const bool ok = qk_wave && head < H;
+    const T* qrow = q + b * q_sb + (ok ? head : 0) * q_sh + 8 * g4;
+#pragma unroll
+    for (int j = 0; j < 18; ++j) {
+      qf[j] = *reinterpret_cast<const i32x4*>(qrow + 32 * j);
+      if (!ok) qf[j] = (i32x4){0, 0, 0, 0};
+    }
+  }
+
+  f32x4 acc[G][4];
+  float m[G], l[G];   // running maximum (log2 domain) and sum of head c16 of every group
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    m[g] = -INFINITY;
+    l[g] = 0.f;
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) acc[g][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+
+  const uint32_t k_addr = lds_base + (16 * sub + c16) * MLA_ROWB + g4 * 16;
+  const uint32_t v_addr = lds_base + g4 * MLA_ROWB + (64 * wave + c16) * 2;
+  const uint32_t pw_addr = lds_base + P_OFF + gq * MLA_PGRP + c16 * MLA_PROW + (4 * sub + g4) * 2;
+  const uint32_t pr_addr = lds_base + P_OFF + c16 * MLA_PROW + g4 * 16;
+  const uint32_t max_addr = lds_base + MAX_OFF + c16 * 4, sum_addr = lds_base + SUM_OFF + c16 * 4;
+
+  int pgA[MLA_PER], pgB[MLA_PER];
+  table_load(0, pgA);
+  stage_rows(0, 0, pgA);
+  asm volatile("" ::: "memory");
+  table_load(1, pgB);
+  table_load(2, pgA);
+  asm volatile("" ::: "memory");
+  stage_rows(1, 1, pgB);
+
+  // one tile: `cur` holds the table entries of tile t + 2, `nxt` receives those of tile t + 3
+  auto step = [&](int t, int stage, int (&cur_pg)[MLA_PER], int (&nxt_pg)[MLA_PER]) {
+    // tile t has landed: since the previous tile's wait this lane issued the table loads of tile t + 2
+    // and then the 5 DMA of tile t + 1; everything but those 5 youngest operations is complete (a
+    // different issue order would only make this wait longer).  Tiles past the split's end are staged
+    // like any other (they re-read the last token's row into a stage nobody reads): the loop has no
+    // branch around its loads, which keeps the compiler's own wait counts exact.
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(MLA_PER) : "memory");
+    lds_barrier();   // everybody's part of tile t has landed; everybody is past tile t - 1
+    table_load(t + 3, nxt_pg);
+    asm volatile("" ::: "memory");   // table loads first, DMA last
+    stage_rows(t + 2, stage >= 1 ? stage - 1 : MLA_NST - 1, cur_pg);   // (t + 2) % 3
+
+    const uint32_t so = stage * MLA_STAGE;
+    const int nv = min(MLA_T, end - start - t * MLA_T);   // valid tokens of the tile
+
+    // ---- S = K q^T for this wave's item
+    float sv[4];
+    if (qk_wave) {
+      f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+      static_for<6>([&](auto jc) {
+        constexpr int j0 = decltype(jc)::value * 3;
+        i32x4 kf[3];
+        lds_read3<j0 * 64>(k_addr + so, kf);
+        s0 = Mma<T>::mfma(__builtin_bit_cast(uint4, kf[0]), __builtin_bit_cast(uint4, qf[j0]), s0);
+        s1 = Mma<T>::mfma(__builtin_bit_cast(uint4, kf[1]), __builtin_bit_cast(uint4, qf[j0 + 1]), s1);
+        s0 = Mma<T>::mfma(__builtin_bit_cast(uint4, kf[2]), __builtin_bit_cast(uint4, qf[j0 + 2]), s0);
+      });
+      float lmax = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        sv[r] = 16 * sub + 4 * g4 + r < nv ? (s0[r] + s1[r]) * scale2 : -INFINITY;
+        lmax = fmaxf(lmax, sv[r]);
+      }
+      lmax = fmaxf(lmax, __shfl_xor(lmax, 16, 64));
+      lmax = fmaxf(lmax, __shfl_xor(lmax, 32, 64));
+      if (g4 == 0) lds_write_b32(max_addr + wave * 64, lmax);
+    }
+    lds_barrier();
+
+    // ---- new maxima of all groups; every tile holds a valid token, so they are finite
+    // (the accumulators and sums are rescaled here, so that the factors are dead before the PV phase)
+    {
+      float wm[NQ];
+      lds_read_f32<NQ>(max_addr, wm);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const float mn = fmaxf(m[g], fmaxf(wm[g], wm[g + G]));
+        const float alpha = fast_exp2(m[g] - mn);
+        m[g] = mn;
+        l[g] *= alpha;
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[g][ct] *= alpha;
+      }
+    }
+    if (qk_wave) {
+      float mq = m[0];
+#pragma unroll
+      for (int g = 1; g < G; ++g) mq = gq == g ? m[g] : mq;
+      float psum = 0.f;
+      uint32_t pb[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = fast_exp2(sv[r] - mq);
+        psum += p;
+        pb[r] = bits16(from_f32<T>(p));
+      }
+      psum += __shfl_xor(psum, 16, 64);
+      psum += __shfl_xor(psum, 32, 64);
+      if (g4 == 0) lds_write_b32(sum_addr + wave * 64, psum);
+      // token 16 sub + 4 g4 + r = contraction slot (r, 4 sub + g4)
+      lds_write_b16<0>(pw_addr, pb[0]);
+      lds_write_b16<16>(pw_addr, pb[1]);
+      lds_write_b16<32>(pw_addr, pb[2]);
+      lds_write_b16<48>(pw_addr, pb[3]);
+    }
+    lds_barrier();
+
+    // ---- O^T += V^T P^T on this wave's 64 columns, all groups
+    {
+      float ws[NQ];
+      lds_read_f32<NQ>(sum_addr, ws);
+#pragma unroll
+      for (int g = 0; g < G; ++g) l[g] += ws[g] + ws[g + G];
+    }
+    i32x4 pf[G];
+    lds_read_p<G>(pr_addr, pf);
+    static_for<4>([&](auto cc) {
+      constexpr int ct = decltype(cc)::value;
+      const i32x4 vf = lds_read_vt<ct * 32>(v_addr + so);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        acc[g][ct] = Mma<T>::mfma(__builtin_bit_cast(uint4, vf), __builtin_bit_cast(uint4, pf[g]), acc[g][ct]);
+      }
+    });
+  };
+
+  int stage = 0;
+  for (int t = 0; t < ntiles; t += 2) {
+    step(t, stage, pgA, pgB);
+    stage = stage + 1 == MLA_NST ? 0 : stage + 1;
+    if (t + 1 >= ntiles) break;
+    step(t + 1, stage, pgB, pgA);
+    stage = stage + 1 == MLA_NST ? 0 : stage + 1;
+  }
+
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the two tiles staged past the end
+
+  // ---- lane holds O^T[column 64 wave + 16 ct + 4 g4 + r][head c16] of every group
+  const int64_t rows = (int64_t)B * H * S;
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int head = h0 + g * 16 + c16;
+    if (head >= H) continue;
+    const float inv = 1.0f / l[g];
+    const int64_t row = ((int64_t)b * H + head) * S + split;
+    if (S > 1 && wave == 0 && g4 == 0) scratch[rows * MLA_DV + row] = (m[g] + __log2f(l[g])) * kLn2;
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+      const int col = 64 * wave + 16 * ct + 4 * g4;
+      const f32x4 v = acc[g][ct] * inv;
+      if (S > 1) {
+        *reinterpret_cast<f32x4*>(scratch + row * MLA_DV + col) = v;
+      } else {
+        T* op = o + b * o_sb + head * o_sh + col;
+        Vec<T, 4> pk;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pk.v[r] = from_f32<T>(v[r]);
+        if (o_vec) {
+          *reinterpret_cast<Vec<T, 4>*>(op) = pk;
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) op[r] = pk.v[r];
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// merge of the splits (stage 2 of the reference): one workgroup per (sequence, head), 4 columns a thread
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(128) void mla_merge_kernel(T* __restrict__ o, const float* __restrict__ scratch,
+                                                        const int* __restrict__ seq_lens, int B, int H, int S,
+                                                        int64_t o_sb, int64_t o_sh, int o_vec) {
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int len = seq_lens[b];
+  const int col = threadIdx.x * 4;
+  const float* lse = scratch + (int64_t)B * H * S * MLA_DV + (int64_t)bh * S;
+  const float* part = scratch + (int64_t)bh * S * MLA_DV + col;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  float mx = -INFINITY, sum = 0.f;
+  const int L = len > 0 ? (len + S - 1) / S : 1;
+  for (int s = 0; s < S && s * L < len; ++s) {   // the non-empty splits
+    const float e = lse[s];
+    const f32x4 v = *reinterpret_cast<const f32x4*>(part + (int64_t)s * MLA_DV);
+    const float nm = fmaxf(mx, e);
+    const float sc = fast_exp2((mx - nm) * kLog2e), w = fast_exp2((e - nm) * kLog2e);
+    acc = acc * sc + v * w;
+    sum = sum * sc + w;
+    mx = nm;
+  }
+  const float inv = len > 0 ? 1.0f / sum : 0.f;
+  T* op = o + b * o_sb + h * o_sh + col;
+  Vec<T, 4> pk;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) pk.v[r] = from_f32<T>(acc[r] * inv);
+  if (o_vec) {
+    *reinterpret_cast<Vec<T, 4>*>(op) = pk;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) op[r] = pk.v[r];
+  }
+}
+
+}  // namespace va
+
+using namespace va;
+
+template <typename T>
+static void launch_mla(void* o, const void* q, const void* cache, const int* bt, const int* sl, float* scratch, int B,
+                       int H, int S, int page_size, int max_blocks, float sm_scale, int64_t q_sb, int64_t q_sh,
+                       int64_t o_sb, int64_t o_sh, int64_t c_sb, int64_t c_se, int64_t bt_s, hipStream_t st) {
+  // heads per workgroup: 32 once there are more than 16 (the widest variant that compiles without
+  // spilling, see the header); "mla_hpw" forces a variant
+  int hpw = H <= 16 ? 16 : 32;
+  if (g_mla_hpw == 16 || g_mla_hpw == 32) hpw = g_mla_hpw;
+  const int NC = ceil_div(H, hpw);
+  const uint32_t ps_magic = page_size == 1 ? 0xffffffffu : (uint32_t)((1ull << 32) / (uint32_t)page_size);
+  const int o_vec = (o_sb % 4 == 0 && o_sh % 4 == 0 && (((uintptr_t)o) & 7) == 0) ? 1 : 0;
+  const unsigned grid = (unsigned)(ceil_div(B * S, 8) * NC * 8);
+#define ML(G)                                                                                                    \
+  hipLaunchKernelGGL((mla_decode_kernel<T, G>), dim3(grid), dim3(MLA_NT), 0, st, (T*)o, (const T*)q,             \
+                     (const T*)cache, bt, sl, scratch, B, H, S, NC, page_size, ps_magic, max_blocks,              \
+                     sm_scale * kLog2e, q_sb, q_sh, o_sb, o_sh, c_sb, c_se, bt_s, o_vec)
+  if (hpw == 16) ML(1); else ML(2);
+#undef ML
+  if (S > 1)
+    hipLaunchKernelGGL((mla_merge_kernel<T>), dim3(B * H), dim3(128), 0, st, (T*)o, (const float*)scratch, sl, B, H, S,
+                       o_sb, o_sh, o_vec);
+}
+
+extern "C" int vllm_amd_mla_decode(void* o, const void* q, const void* kv_cache, const void* block_table,
+                                   const void* seq_lens, float* attn_logits, int64_t attn_logits_floats, int batch,
+                                   int num_heads, int qk_width, int v_width, int page_size,
+                                   int max_blocks_per_seq, int num_kv_splits, float sm_scale, int64_t q_stride_b,
+                                   int64_t q_stride_h, int64_t o_stride_b, int64_t o_stride_h,
+                                   int64_t cache_block_stride, int64_t cache_entry_stride,
+                                   int64_t block_table_stride, int dtype, int cache_dtype, int kv_dtype,
+                                   int index_bits, void* stream) {
+  const char* op = "mla_decode";
+  const char* form = "q [B, H, 576] and a [num_blocks, page_size, 576] latent cache of the same bfloat16 / float16 "
+                     "type (kv_cache_dtype \"auto\"), v = its first 512 columns, int32 block table and lengths";
+  VA_REQUIRE(batch >= 0 && num_heads >= 1 && page_size >= 1 && max_blocks_per_seq >= 1, VLLM_AMD_EINVAL,
+             "%s: bad shape", op);
+  VA_REQUIRE(qk_width == MLA_DK && v_width == MLA_DV, VLLM_AMD_EUNSUPPORTED,
+             "%s: row width %d / %d is not supported; the supported form is %s", op, qk_width, v_width, form);
+  VA_REQUIRE(kv_dtype == VLLM_AMD_KV_AUTO, VLLM_AMD_EUNSUPPORTED,
+             "%s: an fp8 latent cache is not supported in decode; the supported form is %s", op, form);
+  VA_REQUIRE(dtype == VLLM_AMD_BF16 || dtype == VLLM_AMD_F16, VLLM_AMD_EUNSUPPORTED,
+             "%s: q must be bfloat16 or float16; the supported form is %s", op, form);
+  VA_REQUIRE(cache_dtype == dtype, VLLM_AMD_EUNSUPPORTED,
+             "%s: q and cache dtype mismatch (%d vs %d); the supported form is %s", op, dtype, cache_dtype, form);
+  VA_REQUIRE(index_bits == 32, VLLM_AMD_EUNSUPPORTED, "%s: block table and seq_lens must be int32 (got %d-bit)", op,
+             index_bits);
+  VA_REQUIRE(num_kv_splits >= 1, VLLM_AMD_EINVAL, "%s: num_kv_splits %d < 1", op, num_kv_splits);
+  VA_REQUIRE(num_heads <= 128, VLLM_AMD_EUNSUPPORTED, "%s: num_heads %d > 128", op, num_heads);
+  const int64_t need = (int64_t)batch * num_heads * num_kv_splits * (MLA_DV + 1);
+  VA_REQUIRE(num_kv_splits == 1 || attn_logits_floats >= need, VLLM_AMD_EINVAL,
+             "%s: attn_logits scratch too small: %lld floats, [B, H, num_kv_splits, 513] needs %lld", op,
+             (long long)attn_logits_floats, (long long)need);
+  VA_REQUIRE((int64_t)batch * num_kv_splits < (1ll << 27), VLLM_AMD_EINVAL, "%s: batch * num_kv_splits too large", op);
+  if (batch == 0) return VLLM_AMD_OK;
+  VA_REQUIRE(o && q && kv_cache && block_table && seq_lens && (num_kv_splits == 1 || attn_logits), VLLM_AMD_EINVAL,
+             "%s: null pointer", op);
+  VA_REQUIRE(q_stride_b % 8 == 0 && q_stride_h % 8 == 0 && cache_block_stride % 8 == 0 &&
+                 cache_entry_stride % 8 == 0 && cache_entry_stride >= MLA_DK && (((uintptr_t)q) & 15) == 0 &&
+                 (((uintptr_t)kv_cache) & 15) == 0 && (((uintptr_t)attn_logits) & 15) == 0,
+             VLLM_AMD_EUNSUPPORTED, "%s: q / cache strides must be multiples of 8 elements and q, cache, attn_logits "
+             "16-byte aligned", op);
+  hipStream_t st = (hipStream_t)stream;
+#define MD(T)                                                                                                   \
+  launch_mla<T>(o, q, kv_cache, (const int*)block_table, (const int*)seq_lens, attn_logits, batch, num_heads,   \
+                num_kv_splits, page_size, max_blocks_per_seq, sm_scale, q_stride_b, q_stride_h, o_stride_b,     \
+                o_stride_h, cache_block_stride, cache_entry_stride, block_table_stride, st)
+  if (dtype == VLLM_AMD_BF16) MD(bf16_t); else MD(f16_t);
+#undef MD
+  VA_LAUNCH_CHECK("mla_decode launch");
+  return VLLM_AMD_OK;
+}

@@ -39,6 +39,7 @@ extern int g_uni_decode;
 extern int g_pf_fa;
 extern int g_pf_fa_stagger;
 extern int g_pf_fa_abl;
+extern int g_mla_hpw;   // mla_decode.hip
 
 template <typename cache_t> struct CacheTraits;
 template <> struct CacheTraits<float> { static constexpr int X = 4; };
@@ -590,6 +591,7 @@ extern "C" int vllm_amd_set_tuning(const char* key, int value) {
   if (strcmp(key, "pf_fa") == 0) { g_pf_fa = value; return VLLM_AMD_OK; }
   if (strcmp(key, "pf_fa_abl") == 0) { g_pf_fa_abl = value; return VLLM_AMD_OK; }
   if (strcmp(key, "pf_fa_stagger") == 0) { g_pf_fa_stagger = value; return VLLM_AMD_OK; }
+  if (strcmp(key, "mla_hpw") == 0) { g_mla_hpw = value; return VLLM_AMD_OK; }
   VA_REQUIRE(false, VLLM_AMD_EINVAL, "set_tuning: unknown key %s", key);
 }
 

@@ -208,6 +208,33 @@ void reshape_and_cache_flash(const Tensor& key, const Tensor& value, Tensor& key
       key_cache.stride(2), dt(key), kv(kv_cache_dtype), fptr(k_scale), fptr(v_scale), stream_of(key)));
 }
 
+// csrc/cache_kernels.cu:465-501
+void concat_and_cache_mla(const Tensor& kv_c, const Tensor& k_pe, Tensor& kv_cache, const Tensor& slot_mapping,
+                          const std::string& kv_cache_dtype, const Tensor& scale) {
+  need_devs(kv_c, k_pe, kv_cache, slot_mapping, scale);
+  TORCH_CHECK(kv_c.dim() == 2 && k_pe.dim() == 2 && kv_cache.dim() == 3 && kv_c.stride(1) == 1 && k_pe.stride(1) == 1 &&
+                  kv_cache.stride(2) == 1 && slot_mapping.scalar_type() == at::kLong && slot_mapping.is_contiguous(),
+              "concat_and_cache_mla: kv_c [T, rank], k_pe [T, pe], kv_cache [blocks, block_size, rank + pe] with "
+              "contiguous rows and an int64 slot_mapping are required");
+  TORCH_CHECK(kv_cache.size(2) == kv_c.size(1) + k_pe.size(1), "kv_cache.size(2) == kv_lora_rank + pe_dim");  // :487
+  TORCH_CHECK(slot_mapping.size(0) <= kv_c.size(0) && slot_mapping.size(0) <= k_pe.size(0),
+              "concat_and_cache_mla: slot_mapping is longer than kv_c / k_pe");
+  TORCH_CHECK(k_pe.scalar_type() == kv_c.scalar_type(), "concat_and_cache_mla: kv_c and k_pe differ in dtype");
+  const int kvd = kv(kv_cache_dtype);
+  if (kvd == VLLM_AMD_KV_AUTO) {
+    TORCH_CHECK(kv_cache.scalar_type() == kv_c.scalar_type(), "concat_and_cache_mla: \"auto\" needs a cache of kv_c's dtype");
+  } else {
+    TORCH_CHECK(is_fp8(kv_cache) && scale.scalar_type() == at::kFloat,
+                "concat_and_cache_mla: fp8 needs a byte cache and a float scale");
+  }
+  DevGuard g(kv_c.device());
+  check(vllm_amd_concat_and_cache_mla(kv_c.data_ptr(), k_pe.data_ptr(), kv_cache.data_ptr(),
+                                      (const int64_t*)slot_mapping.data_ptr(), (int)slot_mapping.size(0),
+                                      (int)kv_c.size(1), (int)k_pe.size(1), (int)kv_cache.size(1), kv_c.stride(0),
+                                      k_pe.stride(0), kv_cache.stride(0), kv_cache.stride(1), dt(kv_c), kvd,
+                                      fptr(scale), stream_of(kv_c)));
+}
+
 void convert_fp8(Tensor& dst_cache, const Tensor& src_cache, double scale, const std::string& kv_cache_dtype) {
   need_devs(dst_cache, src_cache);
   (void)kv(kv_cache_dtype);   // validates the string; "auto" is treated as e4m3 (gfx950 has one fp8 KV type)
@@ -545,6 +572,10 @@ void register_all() {
        " Tensor! value_cache, Tensor slot_mapping, str kv_cache_dtype, Tensor k_scale,"
        " Tensor v_scale) -> ()",
        &reshape_and_cache_flash);
+  k.op("concat_and_cache_mla",
+       "concat_and_cache_mla(Tensor kv_c, Tensor k_pe, Tensor! kv_cache, Tensor slot_mapping,"
+       " str kv_cache_dtype, Tensor scale) -> ()",
+       &concat_and_cache_mla);
   k.op("convert_fp8", "convert_fp8(Tensor! dst_cache, Tensor src_cache, float scale, str kv_cache_dtype) -> ()",
        &convert_fp8);
   k.op("copy_blocks",
