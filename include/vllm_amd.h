@@ -199,6 +199,23 @@ int vllm_amd_mla_decode(
     int64_t cache_entry_stride, int64_t block_table_stride, int dtype, int cache_dtype,
     int kv_dtype, int index_bits, void* stream);
 
+/* vllm_amd_mla_decode over the fp8 cache concat_and_cache_mla writes for kv_cache_dtype "fp8" /
+ * "fp8_e4m3" (the reference's MLA backend has no such path: triton_mla.py:134-135 raises).
+ * kv_cache [num_blocks, page_size, 576] e4m3fn BYTES, row value = float(byte) * *kv_scale (device
+ * float[1], read on the device); kv_dtype must be FP8_E4M3, cache_dtype is not consulted;
+ * cache_block_stride / cache_entry_stride are in bytes, multiples of 16, entry stride >= 576, the
+ * cache 16-byte aligned.  q, o, block_table, seq_lens, attn_logits, the split rule and the
+ * zero-length row are those of vllm_amd_mla_decode; q and the probabilities stay 16-bit, the bytes
+ * are widened exactly and the scale is applied in fp32. */
+int vllm_amd_mla_decode_fp8(
+    void* o, const void* q, const void* kv_cache, const void* block_table,
+    const void* seq_lens, float* attn_logits, int64_t attn_logits_floats, int batch,
+    int num_heads, int qk_width, int v_width, int page_size, int max_blocks_per_seq,
+    int num_kv_splits, float sm_scale, int64_t q_stride_b, int64_t q_stride_h,
+    int64_t o_stride_b, int64_t o_stride_h, int64_t cache_block_stride,
+    int64_t cache_entry_stride, int64_t block_table_stride, int dtype, int cache_dtype,
+    int kv_dtype, int index_bits, const float* kv_scale, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* fp8 (e4m3fn) quantisation, input [num_tokens, hidden] contiguous           */
 /* ------------------------------------------------------------------------- */

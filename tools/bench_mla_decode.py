@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """MLA decode (csrc/mla_decode.hip) and the latent cache write on the GPU:
-    python tools/bench_mla_decode.py [--out FILE] [--iters 8]
+    python tools/bench_mla_decode.py [--out FILE] [--iters 8] [--fp8]
+(--fp8: instead of the tables below, the fp8-cache kernel beside the 16-bit one on the same shapes, see fp8_table)
 
 bf16, page size 64, H in {16, 128}, num_kv_splits in {1, 4, 16}; per row: us, TB/s over the algorithmic
 bytes (cache rows once + q + o), PFLOP/s over B * len * H * 2 * (576 + 512), and the share of
@@ -45,10 +46,53 @@ def time_eager(fn, iters):
     return e0.elapsed_time(e1) * 1e-3 / iters
 
 
+def fp8_table(shapes, scale, dev, iters, emit):
+    """--fp8: per shape the 16-bit kernel, the fp8 kernel, the 16-bit kernel again (its two times are the
+    spread a difference has to exceed), each over its own rotating cache copies; TB/s over the bytes each
+    kernel has to move (rows once + q + o)."""
+    from vllm_amd.attention.ops.triton_decode_attention import decode_attention_fwd
+    emit("# MLA decode, bf16 q, page 64, kv_scale 0.5: 16-bit cache (timed twice) and fp8 cache, same run")
+    emit("# shape              H  splits | 16-bit us (1st, 2nd) TB/s | fp8 us   TB/s | fp8 / 16-bit")
+    ks = torch.tensor([0.5], device=dev)
+    for name, lens in shapes:
+        B, tokens = len(lens), sum(lens)
+        nb = -(-max(lens) // PAGE)
+        blocks = B * nb
+        want = int(1.25 * bench.MALL_BYTES)
+        c16 = [torch.randn(blocks, PAGE, 576, device=dev, dtype=torch.bfloat16)
+               for _ in range(max(2, -(-want // (blocks * PAGE * 1152))))]
+        c8 = [(torch.randn(blocks, PAGE, 576, device=dev) * 2).to(torch.float8_e4m3fn).view(torch.uint8)
+              for _ in range(max(2, -(-want // (blocks * PAGE * 576))))]
+        bt = torch.randperm(blocks, device=dev).view(B, nb).to(torch.int32)
+        sl = torch.tensor(lens, dtype=torch.int32, device=dev)
+        for H in (16, 128):
+            q = torch.randn(B, H, 576, device=dev, dtype=torch.bfloat16)
+            o = torch.empty(B, H, 512, device=dev, dtype=torch.bfloat16)
+            for splits in (1, 4, 16):
+                lg = torch.empty(B, H, splits, 513, device=dev, dtype=torch.float32)
+
+                def timed(caches, k_scale):
+                    st = {"i": 0}
+
+                    def fn():
+                        kv = caches[st["i"] % len(caches)].unsqueeze(2)
+                        st["i"] += 1
+                        decode_attention_fwd(q, kv, kv[..., :512], o, bt, sl, lg, splits, scale, PAGE, k_scale=k_scale)
+                    return bench.time_gpu_graph(fn, -(-iters // len(caches)) * len(caches))
+                t16a, t8, t16b = timed(c16, None), timed(c8, ks), timed(c16, None)
+                qo = B * H * (576 + 512) * 2
+                t16 = min(t16a, t16b)
+                emit(f"  {name:17s} {H:3d} {splits:5d}   | {t16a * 1e6:7.1f} {t16b * 1e6:7.1f}   {(tokens * 1152 + qo) / t16 / 1e12:5.2f} | "
+                     f"{t8 * 1e6:7.1f}  {(tokens * 576 + qo) / t8 / 1e12:5.2f} | {t8 / t16:5.2f}")
+        del c16, c8
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=8)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fp8", action="store_true", help="the fp8-cache kernel beside the 16-bit one, same shapes")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         print("bench_mla_decode: no GPU", file=sys.stderr)
@@ -70,6 +114,9 @@ def main():
     shapes = [("64 x 4096", [4096] * 64), ("8 x 32768", [32768] * 8), ("1 x 8192", [8192]),
               ("64 x U[512,4096]", torch.randint(512, 4097, (64,), generator=g).tolist())]
     scale = 576 ** -0.5
+    if a.fp8:
+        fp8_table(shapes, scale, dev, a.iters, emit)
+        return 0
     emit("# MLA decode, bf16, page 64; cache copies rotate through > 1.25 x 256 MiB")
     emit("# shape              H  splits |      us |  TB/s | PFLOP/s | roof (bound) share | torch-composed us")
     for name, lens in shapes:

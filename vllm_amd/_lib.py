@@ -44,6 +44,9 @@ SIGNATURES = {
     "vllm_amd_mla_decode": [
         _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _f, _i64, _i64, _i64, _i64, _i64,
         _i64, _i64, _i, _i, _i, _i, _vp],
+    "vllm_amd_mla_decode_fp8": [
+        _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _f, _i64, _i64, _i64, _i64, _i64,
+        _i64, _i64, _i, _i, _i, _i, _vp, _vp],
     "vllm_amd_static_scaled_fp8_quant": [_vp, _vp, _vp, _i64, _i, _i, _vp],
     "vllm_amd_dynamic_scaled_fp8_quant": [_vp, _vp, _vp, _i64, _i, _i, _vp],
     "vllm_amd_dynamic_per_token_scaled_fp8_quant": [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp],
