@@ -294,6 +294,73 @@ int vllm_amd_scaled_mm_blockwise(void* out, const void* a, const void* b,
                                  int64_t as_stride_k, int64_t bs_stride_k,
                                  int64_t bs_stride_n, int out_dtype, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* Fused MoE experts over block-scaled fp8 weights (csrc/moe_block_fp8.hip)   */
+/* ------------------------------------------------------------------------- */
+
+/* The grouped, block-scaled fp8 GEMM of fused_experts(use_fp8_w8a8=True, block_shape=[128, 128]):
+ * the semantics of the reference's Triton fused_moe_kernel
+ * (vllm/model_executor/layers/fused_moe/fused_moe.py:268-475), no C++ counterpart there.
+ * For every i < *num_tokens_post_padded with t = sorted_token_ids[i] < num_valid_tokens and
+ * e = expert_ids[i / block_size_m]:
+ *   c[t, n] = ((topk_weights[t] if mul_routed_weight) * sum_kb a_scales[t / top_k, kb] *
+ *              b_scales[e, n / 128, kb] * sum_{k in block kb} a[t / top_k, k] b[e, n, k]).to(out_dtype)
+ * with the routed weight applied to the fp32 sum before the single rounding; e == -1 (any id outside
+ * [0, num_experts)) stores zeros; entries t >= num_valid_tokens are padding and store nothing; rows
+ * of c named by no entry are left as they are.
+ * a: e4m3 [num_valid_tokens / top_k, K], row stride lda; a_scales float, element (m, kb) at
+ * a_scales[m*as_stride_m + kb*as_stride_k]; b: e4m3 [E, N, K], K contiguous, element strides
+ * b_stride_e / b_stride_n; b_scales: float [E, ceil(N/128), K/128] through three element strides;
+ * c: [num_valid_tokens, N] of out_dtype (bf16 / f16), row stride ldc; sorted_token_ids: int32,
+ * max_num_tokens_padded entries (its length as moe_align_block_size was given it: with an expert_map
+ * that is num_valid_tokens + GLOBAL experts * (block_size_m - 1), while num_experts here is the local
+ * count E of b and only decides which expert ids store zeros; a smaller bound that is known to hold,
+ * such as num_valid_tokens * block_size_m, may be passed instead); expert_ids: int32, one per
+ * block_size_m entries of that length; num_tokens_post_padded: int32 [1], read on the device (the
+ * grid is the host-side bound max_num_tokens_padded, which also caps the device-side count);
+ * topk_weights: float [num_valid_tokens], may be NULL without
+ * mul_routed_weight.  K % 128 == 0 (else VLLM_AMD_EUNSUPPORTED), N arbitrary, block_size_m 16 or 64;
+ * lda and the weight strides >= K and multiples of 16.  No workspace, nothing synchronised. */
+int vllm_amd_moe_blockwise_gemm(void* c, const void* a, const void* b, const float* a_scales,
+                                const float* b_scales, const int32_t* sorted_token_ids,
+                                const int32_t* expert_ids, const int32_t* num_tokens_post_padded,
+                                const float* topk_weights, int num_valid_tokens, int top_k,
+                                int mul_routed_weight, int block_size_m, int max_num_tokens_padded,
+                                int num_experts, int N, int K,
+                                int64_t lda, int64_t b_stride_e, int64_t b_stride_n, int64_t ldc,
+                                int64_t as_stride_m, int64_t as_stride_k, int64_t bs_stride_e,
+                                int64_t bs_stride_n, int64_t bs_stride_k, int out_dtype, void* stream);
+
+/* Replaces torch.ops._moe_C.moe_align_block_size
+ *   schema csrc/moe/torch_bindings.cpp:18-22, csrc/moe/moe_align_sum_kernels.cu.
+ * topk_ids: int32 [numel].  Every flat index i with 0 <= topk_ids[i] < num_experts appears exactly
+ * once in sorted_token_ids, inside its expert's segment; segments are in expert order, each padded
+ * to a multiple of block_size with the sentinel numel; expert_ids[b] names the segment of block b
+ * (0 past the last used block); *num_tokens_post_pad is the padded total.  Ids outside
+ * [0, num_experts) are skipped.  The order inside a segment is unspecified.
+ * sorted_token_ids holds at least numel + num_experts * (block_size - 1) entries (all written),
+ * expert_ids one per block_size of that bound.  num_experts <= 1024, else VLLM_AMD_EUNSUPPORTED. */
+int vllm_amd_moe_align_block_size(const int32_t* topk_ids, int64_t numel, int num_experts,
+                                  int block_size, int32_t* sorted_token_ids, int32_t* expert_ids,
+                                  int32_t* num_tokens_post_pad, void* stream);
+
+/* No counterpart in the reference (there: silu_and_mul, then per_token_group_quant_fp8).
+ * input: [num_rows, 2 d] f16 / bf16 contiguous.  v = T(T(silu(x)) * y) as silu_and_mul rounds it
+ * (csrc/activation_kernels.cu), then the arithmetic of vllm_amd_per_token_group_fp8_quant with
+ * group_size 128, eps 1e-10, +-448, no ue8m0: out_q e4m3 [num_rows, d] contiguous, out_s float,
+ * element (row, group) at out_s[row*s_stride_row + group*s_stride_group].  d % 128 == 0. */
+int vllm_amd_silu_and_mul_group_quant(void* out_q, float* out_s, const void* input, int64_t num_rows,
+                                      int d, int64_t s_stride_row, int64_t s_stride_group, int dtype,
+                                      void* stream);
+
+/* Replaces torch.ops._moe_C.moe_sum
+ *   schema csrc/moe/torch_bindings.cpp:13, csrc/moe/moe_align_sum_kernels.cu.
+ * out[t, :] = sum_k input[t, k, :]; input [num_tokens, top_k, hidden] and out [num_tokens, hidden]
+ * contiguous, f16 / bf16.  Accumulated in fp32 in k order and rounded once (the reference
+ * accumulates top-k 2 .. 4 in the 16-bit type). */
+int vllm_amd_moe_sum(void* out, const void* input, int64_t num_tokens, int top_k, int hidden_size,
+                     int dtype, void* stream);
+
 /* No counterpart in the reference (its libraries own their workspaces): registers (ws != NULL)
  * or removes (ws == NULL) the CURRENT device's workspace -- `bytes` of caller-owned device
  * memory, 256-byte aligned, valid until replaced or removed; at least 513 KiB, sized for full use
@@ -596,6 +663,8 @@ int vllm_amd_ar_free_shared(void* ptr);
 /*   "mm_block_kernel": form of scaled_mm_blockwise: 0 = by M (streaming kernel */
 /*                 up to M 64, tile kernel above), 1 = tile kernel always,      */
 /*                 2 / 3 = its 128-row / 256-row form always                    */
+/*   "moe_ks":     waves per 16-column strip of moe_blockwise_gemm: 0 = by N    */
+/*                 and K (default), 8 = one strip per workgroup, 2 = four       */
 /* ------------------------------------------------------------------------- */
 int vllm_amd_set_tuning(const char* key, int value);
 /* current value of "pa_balance" / "mm_kernel" / "mm_splitk" (the torch layer asks before it allocates) */

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Fused MoE experts over block-scaled fp8 weights on the GPU:
+    python tools/bench_moe.py [--out FILE] [--tokens 1,16,64,256,4096] [--inter 2048,256] [--iters 4]
+
+DeepSeek-V3 shapes: E 256, top-k 8, hidden 7168, intermediate size I per rank 2048 (TP 1) or 256 (TP 8);
+softmax top-k routing of random logits.  For each of the two grouped GEMMs (w1 [E, 2 I, 7168], w2 [E, 7168, I]):
+device time per call (graph replays, bench.time_gpu_graph) and TB/s over the TOUCHED experts' weight bytes
+against the 8 TB/s HBM peak -- the weights (7.5 + 3.8 GB at I 2048) are far beyond the 256 MiB Infinity Cache,
+so every call streams them.  Yardstick, timed in the same process and alternated with the new path: the
+per-expert loop of cutlass_scaled_mm calls on the same data (gather of the expert's rows, block-scaled GEMM,
+scatter), with the row lists prepared on the host beforehand and the loop captured in a graph too, so its
+launch overhead is NOT counted against it.  Then "moe_ks" 8 against 2 for both GEMMs, block_size_m 16 against
+64, and the whole fused_experts call."""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402
+
+FP8 = torch.float8_e4m3fn
+E, TOPK, H = 256, 8, 7168
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tokens", default="1,16,64,256,4096")
+    ap.add_argument("--inter", default="2048,256")
+    ap.add_argument("--iters", type=int, default=4)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        print("bench_moe: no GPU", file=sys.stderr)
+        return 2
+    from vllm_amd import _custom_ops as ops, _lib
+    from vllm_amd.model_executor.layers.fused_moe import fused_experts, moe_align_block_size
+    from vllm_amd.model_executor.layers.fused_moe.fused_moe import _block_size_m
+    dev = torch.device("cuda", 0)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").close()
+
+    def emit(s):
+        print(s, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(s + "\n")
+
+    def fp8_rand(*shape):   # codes 0 .. 119: finite, positive
+        return torch.randint(0, 120, shape, device=dev, dtype=torch.uint8).view(FP8)
+
+    def time_pair(new, old, iters):
+        t = [bench.time_gpu_graph(f, iters) * 1e6 for f in (old, new, old, new)]
+        return t[1], t[3], t[0], t[2]
+
+    emit(f"# E {E}, top-k {TOPK}, hidden {H}; us per call (two alternated rounds); TB/s = touched experts' weight bytes / "
+         f"time, share of the {bench.HBM_PEAK_GBPS / 1000:.0f} TB/s HBM peak")
+    for inter in (int(x) for x in a.inter.split(",")):
+        w1, w2 = fp8_rand(E, 2 * inter, H), fp8_rand(E, H, inter)
+        w1_s = torch.rand((E, 2 * inter // 128, H // 128), device=dev) * 1e-2
+        w2_s = torch.rand((E, H // 128, inter // 128), device=dev) * 1e-2
+        for tokens in (int(x) for x in a.tokens.split(",")):
+            g = torch.Generator(device=dev).manual_seed(tokens)
+            topk_w, ids = torch.randn((tokens, E), device=dev, generator=g).softmax(-1).topk(TOPK, dim=-1)
+            ids = ids.to(torch.int32)
+            touched = ids.unique().numel()
+            x = torch.randn((tokens, H), device=dev, dtype=torch.bfloat16) / 10
+            slots = tokens * TOPK
+            rows = [torch.nonzero(ids.view(-1) == e).view(-1) for e in range(E)]   # host-prepared, outside the timing
+            rows = [(e, r) for e, r in enumerate(rows) if r.numel()]
+            for name, w, ws, top_k, a_rows in (("w1", w1, w1_s, TOPK, tokens), ("w2", w2, w2_s, 1, slots)):
+                N, K = w.shape[1], w.shape[2]
+                aq, As = fp8_rand(a_rows, K), torch.rand((a_rows, K // 128), device=dev) * 1e-2
+                c = torch.zeros((slots, N), dtype=torch.bfloat16, device=dev)
+                wbytes = touched * N * K
+                tw = topk_w.reshape(-1).contiguous()
+
+                def aligned(bm):
+                    return moe_align_block_size(ids, bm, E)
+
+                def new_call(bm, al):
+                    return lambda: ops.moe_block_fp8_gemm(c, aq, w, As, ws, tw, al[0], al[1], al[2], True, top_k, bm)
+
+                def loop():
+                    for e, r in rows:
+                        src = r // top_k
+                        o = ops.cutlass_scaled_mm(aq[src], w[e].t(), As[src], ws[e].t(), torch.bfloat16)
+                        c[r] = o
+                bm = _block_size_m(tokens, TOPK, E)
+                n1, n2, o1, o2 = time_pair(new_call(bm, aligned(bm)), loop, a.iters)
+                tn = min(n1, n2)
+                emit(f"  I {inter:5d} tokens {tokens:5d} {name} N {N:5d} K {K:5d} bm {bm:2d} touched {touched:3d} | grouped {n1:9.1f} "
+                     f"{n2:9.1f} | loop {o1:9.1f} {o2:9.1f} | loop / grouped {min(o1, o2) / tn:6.2f} | "
+                     f"{wbytes / tn / 1e6:6.2f} TB/s, {wbytes / tn / 1e3 / bench.HBM_PEAK_GBPS:.3f} of peak")
+                t = []
+                for ks, b in ((8, bm), (2, bm), (0, 16), (0, 64)) * 2:
+                    _lib.set_tuning("moe_ks", ks)
+                    t.append(bench.time_gpu_graph(new_call(b, aligned(b)), a.iters) * 1e6)
+                _lib.set_tuning("moe_ks", 0)
+                emit(f"      moe_ks 8: {t[0]:9.1f} {t[4]:9.1f}  moe_ks 2: {t[1]:9.1f} {t[5]:9.1f} | block_size_m 16: {t[2]:9.1f} "
+                     f"{t[6]:9.1f}  64: {t[3]:9.1f} {t[7]:9.1f}")
+            full = lambda: fused_experts(x, w1, w2, topk_w, ids, use_fp8_w8a8=True, w1_scale=w1_s, w2_scale=w2_s,
+                                         block_shape=[128, 128])
+            t = bench.time_gpu_graph(full, a.iters) * 1e6
+            allb = touched * 3 * inter * H
+            emit(f"  I {inter:5d} tokens {tokens:5d} fused_experts (quant, align, w1, act + quant, w2, sum): {t:9.1f} us, "
+                 f"{allb / t / 1e6:6.2f} TB/s over the touched weights")
+        del w1, w2
+        torch.cuda.empty_cache()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -258,3 +258,35 @@ def rms_norm_dynamic_per_token_quant(
 
 def silu_and_mul_quant(out: torch.Tensor, input: torch.Tensor, scale: torch.Tensor) -> None:
     torch.ops._C.silu_and_mul_quant(out, input, scale)
+
+
+# ---- fused MoE (vllm/_custom_ops.py:1512-1522) ---------------------------------------------
+def moe_sum(input: torch.Tensor, output: torch.Tensor):
+    torch.ops._moe_C.moe_sum(input, output)
+
+
+def moe_align_block_size(topk_ids: torch.Tensor, num_experts: int, block_size: int,
+                         sorted_token_ids: torch.Tensor, experts_ids: torch.Tensor,
+                         num_tokens_post_pad: torch.Tensor) -> None:
+    torch.ops._moe_C.moe_align_block_size(topk_ids, num_experts, block_size, sorted_token_ids,
+                                          experts_ids, num_tokens_post_pad)
+
+
+# no reference counterpart: the grouped GEMM there is Triton (fused_moe.py:268-475)
+def moe_block_fp8_gemm(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor, a_scales: torch.Tensor,
+                       b_scales: torch.Tensor, topk_weights: Optional[torch.Tensor],
+                       sorted_token_ids: torch.Tensor, expert_ids: torch.Tensor,
+                       num_tokens_post_padded: torch.Tensor, mul_routed_weight: bool, top_k: int,
+                       block_size_m: int) -> None:
+    """c[t] = (topk_weights[t] *) a[t // top_k] @ b[expert of t].T with 1 x 128 / 128 x 128 block
+    scales, for the flat (token, k) slots t that ``sorted_token_ids`` lists."""
+    torch.ops._C.moe_block_fp8_gemm(c, a, b, a_scales, b_scales, topk_weights, sorted_token_ids,
+                                    expert_ids, num_tokens_post_padded, mul_routed_weight, top_k,
+                                    block_size_m)
+
+
+def silu_and_mul_group_quant(output_q: torch.Tensor, output_s: torch.Tensor,
+                             input: torch.Tensor) -> None:
+    """silu_and_mul of ``input`` [rows, 2 d], quantised in 128-wide groups: fp8 ``output_q``
+    [rows, d] and fp32 ``output_s`` [rows, d / 128] (any strides)."""
+    torch.ops._C.silu_and_mul_group_quant(output_q, output_s, input)

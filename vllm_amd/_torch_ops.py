@@ -4,6 +4,7 @@ The operators of
   torch.ops._C            (csrc/torch_bindings.cpp:45-69, 117-120, 188-211, 422-427, 575-593)
   torch.ops._C_cache_ops  (csrc/torch_bindings.cpp:676-708)
   torch.ops._rocm_C       (csrc/rocm/torch_bindings.cpp:34-56)
+  torch.ops._moe_C        (csrc/moe/torch_bindings.cpp:13-22)
 are implemented and registered IN C++ by ``csrc/torch_shim.cpp`` (libvllm_amd_torch.so), with the
 reference's exact schema strings, for the CUDA(=HIP) dispatch key: each one unpacks tensors into
 raw device pointers / shapes / strides and calls libvllm_amd.so on torch's current stream -- no
@@ -110,6 +111,12 @@ rms_norm_static_fp8_quant = torch.ops._C.rms_norm_static_fp8_quant
 fused_add_rms_norm_static_fp8_quant = torch.ops._C.fused_add_rms_norm_static_fp8_quant
 rms_norm_dynamic_per_token_quant = torch.ops._C.rms_norm_dynamic_per_token_quant
 silu_and_mul_quant = torch.ops._C.silu_and_mul_quant
+moe_align_block_size = torch.ops._moe_C.moe_align_block_size
+moe_sum = torch.ops._moe_C.moe_sum
+#: the grouped block-scaled fp8 GEMM of fused_experts and its activation + quantiser; not reference
+#: ops -- the reference's grouped GEMM is a Triton kernel
+moe_block_fp8_gemm = torch.ops._C.moe_block_fp8_gemm
+silu_and_mul_group_quant = torch.ops._C.silu_and_mul_group_quant
 #: device-side BlockTable.compute_slot_mapping (vllm/v1/worker/block_table.py:84-99); not a
 #: reference op -- the reference does this with numpy on the host
 compute_slot_mapping = torch.ops._vllm_amd_C.compute_slot_mapping

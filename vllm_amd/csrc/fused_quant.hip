@@ -7,7 +7,7 @@
 // All HBM-bound.  The row kernels take one workgroup per token and keep the row in
 // registers between the reduction passes (the reference re-reads it from memory for the
 // variance, for the absmax and for the conversion): one read and one write of the row.
-#include "common.cuh"
+#include "quant_helpers.cuh"
 
 namespace va {
 
@@ -263,16 +263,7 @@ __global__ __launch_bounds__(ROW_THREADS) void row_quant_generic_kernel(
   }
 }
 
-// silu(x) * y -> fp8, 8 elements per thread (activation_kernels.cu:14-89)
-template <typename T>
-__device__ __forceinline__ float silu_mul(T x, T y) {
-  const float xf = to_f32(x);
-  // the hardware exp2 / rcp (each ~1 ulp): the result is rounded to T right away, and the
-  // accurate expf + IEEE division made this HBM-bound op VALU-bound
-  const T a = from_f32<T>(xf * __builtin_amdgcn_rcpf(1.0f + __expf(-xf)));
-  return to_f32(from_f32<T>(to_f32(a) * to_f32(y)));
-}
-
+// silu(x) * y -> fp8, 8 elements per thread (activation_kernels.cu:14-89); silu_mul: quant_helpers.cuh
 // VEC: 8 elements per thread, no index division: workgroup = (token(s), 256 chunks); rows
 // shorter than 256 chunks share a workgroup (2^tpb_log2 tokens, power-of-two chunk pitch).
 template <typename T, bool VEC>

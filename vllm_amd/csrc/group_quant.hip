@@ -23,40 +23,9 @@
 //   * codes are packed four at a time with v_cvt_pk_fp8_f32 and stored 8 B per lane.
 // Scales go out through two element strides, which serves the row-major [T, H/g] layout and
 // the reference's "column-major" one (tokens contiguous).
-#include "common.cuh"
+#include "quant_helpers.cuh"
 
 namespace va {
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-
-// maximum over the P-lane segment of the lane; valid in every lane of the segment
-template <int P>
-__device__ __forceinline__ float seg_max(float v) {
-  v = fmaxf(v, dpp_move<0xB1>(v));    // quad_perm [1,0,3,2]
-  v = fmaxf(v, dpp_move<0x4E>(v));    // quad_perm [2,3,0,1]
-  v = fmaxf(v, dpp_move<0x141>(v));   // row_half_mirror: the other quad of the 8 lanes
-  if constexpr (P >= 16) v = fmaxf(v, dpp_move<0x140>(v));   // row_mirror: the other half row
-  if constexpr (P >= 32) v = fmaxf(v, __shfl_xor(v, 16, 64));
-  if constexpr (P >= 64) v = fmaxf(v, __shfl_xor(v, 32, 64));
-  return v;
-}
-
-template <typename T>
-__device__ __forceinline__ void load8(const T* p, float (&f)[8]) {
-  if constexpr (sizeof(T) == 4) {
-    const float4 lo = *reinterpret_cast<const float4*>(p);
-    const float4 hi = *reinterpret_cast<const float4*>(p + 4);
-    f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w;
-    f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
-  } else {
-    const Vec<T, 8> v = *reinterpret_cast<const Vec<T, 8>*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = to_f32(v.v[j]);
-  }
-}
 
 constexpr int GQ_WAVES = 4;
 
@@ -105,23 +74,8 @@ __global__ __launch_bounds__(GQ_WAVES * 64) void group_quant_kernel(
       out_s[token * s_stride_token + gi * s_stride_group] = s;
     }
 
-    float q[8];
-    const bool slow = lo < 0x0d800000u - 1u || !(s >= 7.9e-31f);   // 2^-100
-    if (__builtin_expect(__any(slow), 0)) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) q[j] = f[j] / s;
-    } else {
-      const Divisor d(s);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) q[j] = div_rn(f[j], d);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q[j] = fminf(fmaxf(q[j], qmin), qmax);
-    int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
-    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], w0, true);
-    int w1 = __builtin_amdgcn_cvt_pk_fp8_f32(q[4], q[5], 0, false);
-    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(q[6], q[7], w1, true);
-    if (ok) *reinterpret_cast<uint2*>(out_q + e) = make_uint2((uint32_t)w0, (uint32_t)w1);
+    const uint2 q = group_quant8(f, s, lo, qmin, qmax);
+    if (ok) *reinterpret_cast<uint2*>(out_q + e) = q;
   }
 }
 

@@ -40,6 +40,7 @@ extern int g_pf_fa;
 extern int g_pf_fa_stagger;
 extern int g_pf_fa_abl;
 extern int g_mla_hpw;   // mla_decode.hip
+extern int g_moe_ks;    // moe_block_fp8.hip
 
 template <typename cache_t> struct CacheTraits;
 template <> struct CacheTraits<float> { static constexpr int X = 4; };
@@ -592,6 +593,7 @@ extern "C" int vllm_amd_set_tuning(const char* key, int value) {
   if (strcmp(key, "pf_fa_abl") == 0) { g_pf_fa_abl = value; return VLLM_AMD_OK; }
   if (strcmp(key, "pf_fa_stagger") == 0) { g_pf_fa_stagger = value; return VLLM_AMD_OK; }
   if (strcmp(key, "mla_hpw") == 0) { g_mla_hpw = value; return VLLM_AMD_OK; }
+  if (strcmp(key, "moe_ks") == 0) { g_moe_ks = value; return VLLM_AMD_OK; }
   VA_REQUIRE(false, VLLM_AMD_EINVAL, "set_tuning: unknown key %s", key);
 }
 

@@ -1,8 +1,8 @@
 // PyTorch-ROCm operator shim over the C ABI (include/vllm_amd.h): the C++ side of
-// torch.ops._C / _C_cache_ops / _rocm_C for the hot path, registered with the reference's
+// torch.ops._C / _C_cache_ops / _rocm_C / _moe_C for the hot path, registered with the reference's
 // schema strings (csrc/torch_bindings.cpp:45-69, 117-120, 188-211, 422-427, 575-593, 676-708;
-// csrc/rocm/torch_bindings.cpp:34-56).  Every implementation unpacks data_ptr / sizes /
-// strides, takes torch's current HIP stream and calls libvllm_amd.so; a non-zero status
+// csrc/rocm/torch_bindings.cpp:34-56; csrc/moe/torch_bindings.cpp:13-22).  Every implementation
+// unpacks data_ptr / sizes / strides, takes torch's current HIP stream and calls libvllm_amd.so; a non-zero status
 // becomes the c10::Error (RuntimeError) the reference's TORCH_CHECK raises.  No tensor is
 // allocated inside an op, except the one-time per-device workspace (ensure_workspace).
 //
@@ -18,6 +18,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -383,6 +384,109 @@ void cutlass_scaled_mm(Tensor& out, const Tensor& a, const Tensor& b, const Tens
                            (int)b_scales.numel(), dt(out), stream_of(a)));
 }
 
+// ---- fused MoE over block-scaled fp8 weights (csrc/moe_block_fp8.hip) ------------------------
+inline bool is_i32(const Tensor& t) { return t.scalar_type() == at::kInt && t.is_contiguous(); }
+
+// csrc/moe/moe_align_sum_kernels.cu (moe_align_block_size)
+void moe_align_block_size(const Tensor& topk_ids, int64_t num_experts, int64_t block_size, Tensor& sorted_token_ids,
+                          Tensor& experts_ids, Tensor& num_tokens_post_pad) {
+  need_devs(topk_ids, sorted_token_ids, experts_ids, num_tokens_post_pad);
+  TORCH_CHECK(is_i32(topk_ids) && is_i32(sorted_token_ids) && is_i32(experts_ids) && is_i32(num_tokens_post_pad),
+              "moe_align_block_size: contiguous int32 tensors required");
+  TORCH_CHECK(block_size > 0 && num_experts >= 0, "moe_align_block_size: block_size > 0 && num_experts >= 0");
+  const int64_t max_padded = topk_ids.numel() + num_experts * (block_size - 1);
+  TORCH_CHECK(sorted_token_ids.numel() >= max_padded &&
+                  experts_ids.numel() >= (max_padded + block_size - 1) / block_size && num_tokens_post_pad.numel() >= 1,
+              "moe_align_block_size: sorted_token_ids needs numel + num_experts * (block_size - 1) entries and "
+              "experts_ids one per block of them");
+  DevGuard g(topk_ids.device());
+  check(vllm_amd_moe_align_block_size((const int32_t*)topk_ids.data_ptr(), topk_ids.numel(), (int)num_experts,
+                                      (int)block_size, (int32_t*)sorted_token_ids.data_ptr(),
+                                      (int32_t*)experts_ids.data_ptr(), (int32_t*)num_tokens_post_pad.data_ptr(),
+                                      stream_of(topk_ids)));
+}
+
+// csrc/moe/moe_align_sum_kernels.cu (moe_sum): input [num_tokens, topk, hidden], output [num_tokens, hidden]
+void moe_sum(const Tensor& input, Tensor& output) {
+  need_devs(input, output);
+  TORCH_CHECK(input.dim() == 3 && output.dim() == 2 && input.size(0) == output.size(0) &&
+                  input.size(2) == output.size(1) && input.size(1) >= 1,
+              "moe_sum: input [num_tokens, topk, hidden], output [num_tokens, hidden]");
+  TORCH_CHECK(input.is_contiguous() && output.is_contiguous() && input.scalar_type() == output.scalar_type(),
+              "moe_sum: contiguous tensors of one dtype required");
+  DevGuard g(input.device());
+  check(vllm_amd_moe_sum(output.data_ptr(), input.data_ptr(), input.size(0), (int)input.size(1), (int)input.size(2),
+                         dt(input), stream_of(input)));
+}
+
+// The grouped GEMM of fused_experts (no reference op: its kernel is Triton, fused_moe.py:268-475).
+// c [num_valid_tokens, N] or [tokens, top_k', N]; a [num_valid_tokens / top_k, K] fp8; b [E, N, K] fp8;
+// a_scales [rows, K/128]; b_scales [E, ceil(N/128), K/128].
+void moe_block_fp8_gemm(Tensor& c, const Tensor& a, const Tensor& b, const Tensor& a_scales, const Tensor& b_scales,
+                        const OptTensor& topk_weights, const Tensor& sorted_token_ids, const Tensor& expert_ids,
+                        const Tensor& num_tokens_post_padded, bool mul_routed_weight, int64_t top_k,
+                        int64_t block_size_m) {
+  need_devs(c, a, b, a_scales, b_scales, topk_weights, sorted_token_ids, expert_ids, num_tokens_post_padded);
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 3 && (c.dim() == 2 || c.dim() == 3) && a_scales.dim() == 2 &&
+                  b_scales.dim() == 3,
+              "moe_block_fp8_gemm: a [rows, K], b [E, N, K], c [rows * top_k, N], a_scales 2-D, b_scales 3-D");
+  const int64_t K = a.size(1), E = b.size(0), N = b.size(1), kb = K / 128, nb = (N + 127) / 128;
+  TORCH_CHECK(c.size(-1) == N && c.stride(-1) == 1 && (c.dim() == 2 || c.stride(0) == c.size(1) * c.stride(1)),
+              "moe_block_fp8_gemm: c must have N contiguous columns and evenly strided rows");
+  const int64_t nvt = N ? c.numel() / N : 0;
+  TORCH_CHECK(top_k >= 1 && a.size(0) * top_k == nvt, "moe_block_fp8_gemm: c rows == a rows * top_k");
+  TORCH_CHECK(b.size(2) == K && a.stride(1) == 1 && b.stride(2) == 1, "moe_block_fp8_gemm: K mismatch / K not contiguous");
+  TORCH_CHECK(is_fp8(a) && is_fp8(b), "moe_block_fp8_gemm: fp8 e4m3 operands required");
+  TORCH_CHECK(c.scalar_type() == at::kBFloat16 || c.scalar_type() == at::kHalf,
+              "moe_block_fp8_gemm: c must be bfloat16 or float16, got ", c.scalar_type());
+  TORCH_CHECK(a_scales.scalar_type() == at::kFloat && b_scales.scalar_type() == at::kFloat && a_scales.size(0) == a.size(0) &&
+                  a_scales.size(1) == kb && b_scales.size(0) == E && b_scales.size(1) == nb && b_scales.size(2) == kb,
+              "moe_block_fp8_gemm: float32 a_scales [rows, K/128] and b_scales [E, ceil(N/128), K/128] required");
+  TORCH_CHECK(is_i32(sorted_token_ids) && is_i32(expert_ids) && is_i32(num_tokens_post_padded),
+              "moe_block_fp8_gemm: contiguous int32 sorted_token_ids / expert_ids / num_tokens_post_padded required");
+  TORCH_CHECK(block_size_m > 0, "moe_block_fp8_gemm: block_size_m > 0");
+  // the grid and the cap of the device-side count come from the length of sorted_token_ids, as in the
+  // reference's launch (fused_moe.py:519-528): with an expert_map it was aligned for the global expert
+  // count; and as there, never more than one block per slot (every non-empty expert holds a slot)
+  const int64_t max_padded = std::min<int64_t>(sorted_token_ids.numel(), nvt * block_size_m);
+  TORCH_CHECK(sorted_token_ids.numel() >= nvt && max_padded < INT32_MAX &&
+                  expert_ids.numel() >= (max_padded + block_size_m - 1) / block_size_m &&
+                  num_tokens_post_padded.numel() >= 1,
+              "moe_block_fp8_gemm: sorted_token_ids holds fewer entries than c has rows, or expert_ids fewer than one "
+              "per block_size_m entries of it");
+  TORCH_CHECK(!mul_routed_weight || topk_weights.has_value(), "moe_block_fp8_gemm: mul_routed_weight needs topk_weights");
+  TORCH_CHECK(!topk_weights.has_value() || (topk_weights->scalar_type() == at::kFloat && topk_weights->is_contiguous() &&
+                                            topk_weights->numel() == nvt),
+              "moe_block_fp8_gemm: topk_weights must be contiguous float32 with one entry per row of c");
+  DevGuard g(a.device());
+  check(vllm_amd_moe_blockwise_gemm(
+      c.data_ptr(), a.data_ptr(), b.data_ptr(), fptr(a_scales), fptr(b_scales),
+      (const int32_t*)sorted_token_ids.data_ptr(), (const int32_t*)expert_ids.data_ptr(),
+      (const int32_t*)num_tokens_post_padded.data_ptr(), fptr(topk_weights), (int)nvt, (int)top_k,
+      mul_routed_weight ? 1 : 0, (int)block_size_m, (int)max_padded, (int)E, (int)N, (int)K, a.stride(0), b.stride(0), b.stride(1),
+      c.stride(-2), a_scales.stride(0), a_scales.stride(1), b_scales.stride(0), b_scales.stride(1), b_scales.stride(2),
+      dt(c), stream_of(a)));
+}
+
+// silu_and_mul + per_token_group_fp8_quant (group 128) in one pass; input [rows, 2 d]
+void silu_and_mul_group_quant(Tensor& output_q, Tensor& output_s, const Tensor& input) {
+  need_devs(output_q, output_s, input);
+  fp8_out(output_q);
+  TORCH_CHECK(input.dim() == 2 && input.is_contiguous() && input.size(1) % 2 == 0,
+              "silu_and_mul_group_quant: contiguous input [rows, 2 * d] required");
+  const int64_t rows = input.size(0), d = input.size(1) / 2;
+  TORCH_CHECK(input.scalar_type() == at::kBFloat16 || input.scalar_type() == at::kHalf,
+              "silu_and_mul_group_quant: input must be bfloat16 or float16, got ", input.scalar_type());
+  TORCH_CHECK(output_q.dim() == 2 && output_q.size(0) == rows && output_q.size(1) == d && output_s.dim() == 2 &&
+                  output_s.scalar_type() == at::kFloat &&
+                  output_s.size(0) == rows && output_s.size(1) == d / 128,
+              "silu_and_mul_group_quant: output_q [rows, d], output_s float32 [rows, d / 128]");
+  DevGuard g(input.device());
+  check(vllm_amd_silu_and_mul_group_quant(output_q.data_ptr(), (float*)output_s.data_ptr(), input.data_ptr(), rows,
+                                          (int)d, output_s.stride(0), output_s.stride(1), dt(input),
+                                          stream_of(input)));
+}
+
 void wvSplitKQ(const Tensor& in_a, const Tensor& in_b, Tensor& out_c, const Tensor& scale_a, const Tensor& scale_b,
                int64_t cu_count) {
   need_devs(in_a, in_b, out_c, scale_a, scale_b);
@@ -561,6 +665,26 @@ void register_all() {
        "rms_norm_dynamic_per_token_quant(Tensor! result, Tensor input, Tensor weight,"
        " Tensor! scale, float epsilon, Tensor? scale_ub, Tensor!? residual) -> ()",
        &rms_norm_dynamic_per_token_quant);
+
+  // no reference counterpart (its grouped GEMM is Triton, its activation and quantiser two ops)
+  c.op("moe_block_fp8_gemm",
+       "moe_block_fp8_gemm(Tensor! c, Tensor a, Tensor b, Tensor a_scales, Tensor b_scales,"
+       " Tensor? topk_weights, Tensor sorted_token_ids, Tensor expert_ids,"
+       " Tensor num_tokens_post_padded, bool mul_routed_weight, int top_k, int block_size_m) -> ()",
+       &moe_block_fp8_gemm);
+  c.op("silu_and_mul_group_quant",
+       "silu_and_mul_group_quant(Tensor! output_q, Tensor! output_s, Tensor input) -> ()",
+       &silu_and_mul_group_quant);
+
+  // csrc/moe/torch_bindings.cpp:13-22
+  Registrar mo = open_ns("_moe_C");
+  mo.op("moe_sum", "moe_sum(Tensor input, Tensor! output) -> ()", &moe_sum);
+  mo.op("moe_align_block_size",
+        "moe_align_block_size(Tensor topk_ids, int num_experts,"
+        "                     int block_size, Tensor! sorted_token_ids,"
+        "                     Tensor! experts_ids,"
+        "                     Tensor! num_tokens_post_pad) -> ()",
+        &moe_align_block_size);
 
   Registrar k = open_ns("_C_cache_ops");
   k.op("reshape_and_cache",

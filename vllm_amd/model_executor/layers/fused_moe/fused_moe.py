@@ -1,0 +1,156 @@
+"""Fused MoE experts over block-scaled fp8 weights, with the names and arguments of the
+reference's ``vllm/model_executor/layers/fused_moe/fused_moe.py`` (fused_experts :1253-1346,
+fused_experts_impl :1349-1563, invoke_fused_moe_kernel :478-640).
+
+Supported: ``use_fp8_w8a8=True`` with ``block_shape == [128, 128]``, silu with mul, dynamic
+activation scales, bf16 / f16 hidden states.  One layer is five launches and a sum, all HIP
+kernels of libvllm_amd.so, plus the zero fill of the second GEMM's output, with no host
+synchronisation (graph-capturable):
+
+  per_token_group_fp8_quant -> moe_align_block_size -> moe_block_fp8_gemm (w1)
+  -> silu_and_mul_group_quant -> moe_block_fp8_gemm (w2, routed weights) -> moe_sum
+
+Anything else raises NotImplementedError naming the argument: there is no eager or Triton
+fallback.  Routing (fused_topk / grouped_topk) is the caller's: it passes topk_weights / topk_ids."""
+from __future__ import annotations
+
+from typing import Any, Optional
+
+import torch
+
+from .... import _custom_ops as ops
+from ....quantization.fp8_utils import per_token_group_quant_fp8
+from .moe_align_block_size import moe_align_block_size
+
+#: tokens per pass (VLLM_FUSED_MOE_CHUNK_SIZE's default in the reference, fused_moe.py:1402)
+CHUNK_SIZE = 32768
+
+
+def _block_size_m(num_tokens: int, top_k: int, num_experts: int) -> int:
+    # 16 sorted rows per workgroup while an expert sees 16 slots or fewer on average (padding to 64
+    # would then stream every touched expert's weights for mostly empty MFMA tiles), 64 above.
+    # Measured at E 256, top-k 8 (tools/bench_moe.py, profiles/moe_block_fp8.txt): 16 is 1.5 - 2.2 x
+    # faster than 64 from 1 to 256 tokens, 64 is 1.06 - 1.32 x faster at 4096 tokens; the crossover
+    # itself (between 256 and 4096 tokens) is not measured, the rule puts it at 512.
+    return 16 if num_tokens * top_k <= 16 * num_experts else 64
+
+
+def invoke_fused_moe_kernel(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor,
+                            A_scale: Optional[torch.Tensor], B_scale: Optional[torch.Tensor],
+                            B_zp: Optional[torch.Tensor], topk_weights: Optional[torch.Tensor],
+                            sorted_token_ids: torch.Tensor, expert_ids: torch.Tensor,
+                            num_tokens_post_padded: torch.Tensor, mul_routed_weight: bool, top_k: int,
+                            config: dict[str, Any], compute_type: Any = None,
+                            use_fp8_w8a8: bool = False, use_int8_w8a8: bool = False,
+                            use_int8_w8a16: bool = False, use_int4_w4a16: bool = False,
+                            per_channel_quant: bool = False,
+                            block_shape: Optional[list[int]] = None) -> None:
+    """The grouped GEMM: C[t] = (topk_weights[t] *) A[t // top_k] @ B[expert of slot t].T for the
+    slots ``sorted_token_ids`` lists; ``config["BLOCK_SIZE_M"]`` is the block size the ids were
+    aligned to (16 or 64).  ``compute_type`` is implied by C's dtype."""
+    for name, flag in (("use_int8_w8a8", use_int8_w8a8), ("use_int8_w8a16", use_int8_w8a16),
+                       ("use_int4_w4a16", use_int4_w4a16), ("per_channel_quant", per_channel_quant)):
+        if flag:
+            raise NotImplementedError(f"invoke_fused_moe_kernel: {name} is not implemented on gfx950")
+    if not use_fp8_w8a8:
+        raise NotImplementedError("invoke_fused_moe_kernel: only use_fp8_w8a8=True is implemented")
+    if block_shape is None or list(block_shape) != [128, 128]:
+        raise NotImplementedError("invoke_fused_moe_kernel: block_shape must be [128, 128]")
+    if B_zp is not None:
+        raise NotImplementedError("invoke_fused_moe_kernel: B_zp is not implemented")
+    assert topk_weights is not None or not mul_routed_weight
+    assert topk_weights is None or topk_weights.stride(-1) == 1
+    assert sorted_token_ids.stride(0) == 1
+    assert A_scale is not None and B_scale is not None
+    assert -(-B.size(-2) // 128) == B_scale.size(-2) and -(-B.size(-1) // 128) == B_scale.size(-1)
+    tw = None
+    if topk_weights is not None:
+        tw = topk_weights.reshape(-1)
+        if tw.dtype != torch.float32:
+            tw = tw.float()
+    ops.moe_block_fp8_gemm(C, A, B, A_scale, B_scale, tw, sorted_token_ids, expert_ids,
+                           num_tokens_post_padded, mul_routed_weight, top_k, config["BLOCK_SIZE_M"])
+
+
+def fused_experts(hidden_states: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
+                  topk_weights: torch.Tensor, topk_ids: torch.Tensor, inplace: bool = False,
+                  activation: str = "silu", is_act_and_mul: bool = True,
+                  apply_router_weight_on_input: bool = False, use_fp8_w8a8: bool = False,
+                  use_int8_w8a8: bool = False, use_int8_w8a16: bool = False,
+                  use_int4_w4a16: bool = False, use_mxfp4_w4a4: bool = False,
+                  per_channel_quant: bool = False, global_num_experts: int = -1,
+                  expert_map: Optional[torch.Tensor] = None,
+                  w1_scale: Optional[torch.Tensor] = None, w2_scale: Optional[torch.Tensor] = None,
+                  w1_zp: Optional[torch.Tensor] = None, w2_zp: Optional[torch.Tensor] = None,
+                  a1_scale: Optional[torch.Tensor] = None, a2_scale: Optional[torch.Tensor] = None,
+                  block_shape: Optional[list[int]] = None, allow_deep_gemm: bool = False,
+                  allow_cutlass_block_scaled_grouped_gemm: bool = False) -> torch.Tensor:
+    """hidden_states [M, K]; w1 [E, 2 I, K] and w2 [E, K, I] fp8 e4m3 with w1_scale
+    [E, ceil(2 I / 128), K / 128] and w2_scale [E, ceil(K / 128), I / 128]; topk_weights / topk_ids
+    [M, top_k].  Returns sum_k topk_weights[m, k] * expert_{topk_ids[m, k]}(hidden_states[m]), written
+    into ``hidden_states`` with ``inplace``.  A slot whose id is outside [0, global_num_experts) adds
+    nothing; with ``expert_map`` (global -> local index, -1 = absent) w1 / w2 hold the local experts."""
+    for name, flag in (("use_int8_w8a8", use_int8_w8a8), ("use_int8_w8a16", use_int8_w8a16),
+                       ("use_int4_w4a16", use_int4_w4a16), ("use_mxfp4_w4a4", use_mxfp4_w4a4),
+                       ("per_channel_quant", per_channel_quant)):
+        if flag:
+            raise NotImplementedError(f"fused_experts: {name} is not implemented on gfx950")
+    if not use_fp8_w8a8:
+        raise NotImplementedError("fused_experts: only use_fp8_w8a8=True is implemented")
+    if block_shape is None or list(block_shape) != [128, 128]:
+        raise NotImplementedError("fused_experts: block_shape must be [128, 128]")
+    if activation != "silu" or not is_act_and_mul:
+        raise NotImplementedError(
+            f"fused_experts: activation={activation!r}, is_act_and_mul={is_act_and_mul}: only silu "
+            "with mul is implemented")
+    for name, val in (("a1_scale", a1_scale), ("a2_scale", a2_scale), ("w1_zp", w1_zp), ("w2_zp", w2_zp)):
+        if val is not None:
+            raise NotImplementedError(f"fused_experts: {name} is not implemented (activation scales are dynamic)")
+    if hidden_states.dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"fused_experts: hidden_states dtype {hidden_states.dtype} is not implemented")
+    assert w1_scale is not None and w2_scale is not None, "block-scaled weights need their scales"
+    assert hidden_states.size(1) == w1.size(2), f"Hidden size mismatch {hidden_states.size(1)} != {w1.size(2)}"
+    assert topk_weights.size() == topk_ids.size(), "topk shape mismatch"
+    assert hidden_states.is_contiguous(), "Hidden_states must be contiguous"
+    assert w1.stride(-1) == 1 and w2.stride(-1) == 1, "Stride of last dimension must be 1"
+
+    num_tokens = hidden_states.size(0)
+    E, N, _ = w1.size()
+    K = w2.size(1)
+    assert w2.size(2) * 2 == N, "w1 holds gate and up: [E, 2 I, K] against w2 [E, K, I]"
+    if global_num_experts == -1:
+        global_num_experts = E
+    top_k = topk_ids.size(1)
+    if apply_router_weight_on_input:
+        assert top_k == 1, "apply_router_weight_on_input is only implemented for topk=1"
+    out = hidden_states if inplace else torch.empty_like(hidden_states)
+    if topk_ids.dtype != torch.int32:
+        topk_ids = topk_ids.to(torch.int32)
+    if topk_weights.dtype != torch.float32:
+        topk_weights = topk_weights.float()
+    dev, dtype = hidden_states.device, hidden_states.dtype
+
+    for begin in range(0, num_tokens, CHUNK_SIZE):
+        end = min(begin + CHUNK_SIZE, num_tokens)
+        m = end - begin
+        ids, weights = topk_ids[begin:end], topk_weights[begin:end].contiguous()
+        config = {"BLOCK_SIZE_M": _block_size_m(m, top_k, global_num_experts)}
+        cache1 = torch.empty((m * top_k, N), device=dev, dtype=dtype)
+        # zeros: a slot whose id is outside [0, global_num_experts) is in no expert's run, so neither GEMM
+        # writes its row, and moe_sum must add nothing for it (cache1 / q2 rows of such slots are never read)
+        cache3 = torch.zeros((m, top_k, K), device=dev, dtype=dtype)
+        q2 = torch.empty((m * top_k, N // 2), device=dev, dtype=ops.FP8_DTYPE)
+        s2 = torch.empty((m * top_k, N // 256), device=dev, dtype=torch.float32)
+
+        q1, s1 = per_token_group_quant_fp8(hidden_states[begin:end], 128)
+        sorted_ids, expert_ids, num_post = moe_align_block_size(ids, config["BLOCK_SIZE_M"],
+                                                                global_num_experts, expert_map)
+        invoke_fused_moe_kernel(q1, w1, cache1, s1, w1_scale, None, weights, sorted_ids, expert_ids, num_post,
+                                apply_router_weight_on_input, top_k, config, use_fp8_w8a8=True,
+                                block_shape=block_shape)
+        ops.silu_and_mul_group_quant(q2, s2, cache1)
+        invoke_fused_moe_kernel(q2, w2, cache3, s2, w2_scale, None, weights, sorted_ids, expert_ids, num_post,
+                                not apply_router_weight_on_input, 1, config, use_fp8_w8a8=True,
+                                block_shape=block_shape)
+        ops.moe_sum(cache3, out[begin:end])
+    return out
