@@ -361,6 +361,43 @@ int vllm_amd_silu_and_mul_group_quant(void* out_q, float* out_s, const void* inp
 int vllm_amd_moe_sum(void* out, const void* input, int64_t num_tokens, int top_k, int hidden_size,
                      int dtype, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* MoE routing (csrc/moe_routing.hip): one launch per call, nothing allocated */
+/* or synchronised.  Ties go to the lower expert (and group) index; ids come  */
+/* in descending order of the selecting score, are distinct and lie in        */
+/* [0, num_experts) whatever the logits hold.  num_experts <= 1024 and        */
+/* 1 <= topk <= min(num_experts, 64), else VLLM_AMD_EUNSUPPORTED;             */
+/* num_tokens == 0 returns 0 without a launch.                                */
+/* ------------------------------------------------------------------------- */
+enum { VLLM_AMD_SCORE_SOFTMAX = 0, VLLM_AMD_SCORE_SIGMOID = 1 };
+
+/* Replaces torch.ops._moe_C.topk_softmax
+ *   schema csrc/moe/torch_bindings.cpp:6-9, csrc/moe/topk_softmax_kernels.cu,
+ * and the division by the sum that fused_topk (fused_moe.py:882-915) appends with `renormalize`.
+ * p = softmax(gating_output[t, :]) in fp32; topk_weights [num_tokens, topk] float = the topk largest p
+ * (divided by their sum with renormalize), topk_ids the experts (int32, or int64 with ids_int64 = 1),
+ * token_expert_indices[t, k] = k * num_tokens + t (int32).  gating_output: [num_tokens, num_experts]
+ * of gating_dtype (F32 / F16 / BF16), experts contiguous, row stride gating_stride elements. */
+int vllm_amd_topk_softmax(float* topk_weights, void* topk_ids, int32_t* token_expert_indices,
+                          const void* gating_output, int64_t num_tokens, int num_experts, int topk,
+                          int64_t gating_stride, int renormalize, int gating_dtype, int ids_int64,
+                          void* stream);
+
+/* The reference's torch grouped_topk (vllm/model_executor/layers/fused_moe/fused_moe.py:920-975; no
+ * C++ counterpart there).  scores = softmax or sigmoid (scoring_func: VLLM_AMD_SCORE_*) of the logits
+ * in fp32; sel = scores + e_score_correction_bias (float [num_experts], may be NULL: sel = scores).
+ * The experts form num_expert_group groups of consecutive experts; a group's score is the sum of its
+ * two largest sel with a bias and its largest sel without; the topk_group best groups survive; the
+ * topk largest sel among their experts give topk_ids (int32); topk_weights (float) are the UNBIASED
+ * scores of those ids, divided by their sum with renormalize.  num_expert_group divides num_experts,
+ * 1 <= topk_group <= num_expert_group, topk <= topk_group * (num_experts / num_expert_group), a bias
+ * needs groups of at least 2 experts (else VLLM_AMD_EINVAL).  Groups that do not cover a power-of-two
+ * number of whole lanes (see moe_routing.hip) are limited to num_expert_group <= 64. */
+int vllm_amd_grouped_topk(float* topk_weights, int32_t* topk_ids, const void* gating_output,
+                          const float* e_score_correction_bias, int64_t num_tokens, int num_experts,
+                          int topk, int num_expert_group, int topk_group, int scoring_func,
+                          int renormalize, int64_t gating_stride, int gating_dtype, void* stream);
+
 /* No counterpart in the reference (its libraries own their workspaces): registers (ws != NULL)
  * or removes (ws == NULL) the CURRENT device's workspace -- `bytes` of caller-owned device
  * memory, 256-byte aligned, valid until replaced or removed; at least 513 KiB, sized for full use

@@ -272,6 +272,26 @@ def moe_align_block_size(topk_ids: torch.Tensor, num_experts: int, block_size: i
                                           experts_ids, num_tokens_post_pad)
 
 
+def topk_softmax(topk_weights: torch.Tensor, topk_ids: torch.Tensor, token_expert_indices: torch.Tensor,
+                 gating_output: torch.Tensor) -> None:
+    torch.ops._moe_C.topk_softmax(topk_weights, topk_ids, token_expert_indices, gating_output)
+
+
+# no reference counterparts: there fused_topk divides by the sum in torch and grouped_topk is torch code
+def fused_topk(topk_weights: torch.Tensor, topk_ids: torch.Tensor, token_expert_indices: torch.Tensor,
+               gating_output: torch.Tensor, renormalize: bool) -> None:
+    """topk_softmax with the optional division by the weights' sum inside the same launch."""
+    torch.ops._moe_C.fused_topk(topk_weights, topk_ids, token_expert_indices, gating_output, renormalize)
+
+
+def grouped_topk(topk_weights: torch.Tensor, topk_ids: torch.Tensor, gating_output: torch.Tensor,
+                 e_score_correction_bias: Optional[torch.Tensor], num_expert_group: int, topk_group: int,
+                 renormalize: bool, scoring_func: str) -> None:
+    """Group-limited routing in one launch: fp32 ``topk_weights`` and int32 ``topk_ids`` [tokens, topk]."""
+    torch.ops._moe_C.grouped_topk(topk_weights, topk_ids, gating_output, e_score_correction_bias,
+                                  num_expert_group, topk_group, renormalize, scoring_func)
+
+
 # no reference counterpart: the grouped GEMM there is Triton (fused_moe.py:268-475)
 def moe_block_fp8_gemm(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor, a_scales: torch.Tensor,
                        b_scales: torch.Tensor, topk_weights: Optional[torch.Tensor],

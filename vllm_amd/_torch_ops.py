@@ -4,7 +4,7 @@ The operators of
   torch.ops._C            (csrc/torch_bindings.cpp:45-69, 117-120, 188-211, 422-427, 575-593)
   torch.ops._C_cache_ops  (csrc/torch_bindings.cpp:676-708)
   torch.ops._rocm_C       (csrc/rocm/torch_bindings.cpp:34-56)
-  torch.ops._moe_C        (csrc/moe/torch_bindings.cpp:13-22)
+  torch.ops._moe_C        (csrc/moe/torch_bindings.cpp:6-22)
 are implemented and registered IN C++ by ``csrc/torch_shim.cpp`` (libvllm_amd_torch.so), with the
 reference's exact schema strings, for the CUDA(=HIP) dispatch key: each one unpacks tensors into
 raw device pointers / shapes / strides and calls libvllm_amd.so on torch's current stream -- no
@@ -113,6 +113,11 @@ rms_norm_dynamic_per_token_quant = torch.ops._C.rms_norm_dynamic_per_token_quant
 silu_and_mul_quant = torch.ops._C.silu_and_mul_quant
 moe_align_block_size = torch.ops._moe_C.moe_align_block_size
 moe_sum = torch.ops._moe_C.moe_sum
+topk_softmax = torch.ops._moe_C.topk_softmax
+#: routing in one launch each (csrc/moe_routing.hip); not reference ops -- the reference renormalises
+#: fused_topk's result in torch and its grouped_topk is torch code
+fused_topk = torch.ops._moe_C.fused_topk
+grouped_topk = torch.ops._moe_C.grouped_topk
 #: the grouped block-scaled fp8 GEMM of fused_experts and its activation + quantiser; not reference
 #: ops -- the reference's grouped GEMM is a Triton kernel
 moe_block_fp8_gemm = torch.ops._C.moe_block_fp8_gemm

@@ -468,6 +468,60 @@ void moe_block_fp8_gemm(Tensor& c, const Tensor& a, const Tensor& b, const Tenso
       dt(c), stream_of(a)));
 }
 
+// ---- MoE routing (csrc/moe_routing.hip) --------------------------------------------------------
+// gating_output [tokens, experts] float32 / float16 / bfloat16 with contiguous experts; outputs [tokens, topk]
+void route_check(const char* op, const Tensor& w, const Tensor& ids, const Tensor& gating) {
+  TORCH_CHECK(gating.dim() == 2 && (gating.size(1) <= 1 || gating.stride(1) == 1) && is_16_32(gating), op,
+              ": gating_output must be [num_tokens, num_experts] float32 / float16 / bfloat16 with contiguous experts");
+  TORCH_CHECK(w.dim() == 2 && w.size(0) == gating.size(0) && w.scalar_type() == at::kFloat && w.is_contiguous(), op,
+              ": topk_weights must be contiguous float32 [num_tokens, topk]");
+  TORCH_CHECK(ids.sizes() == w.sizes() && ids.is_contiguous(), op, ": topk_ids must be contiguous [num_tokens, topk]");
+}
+
+// fused_topk's whole device work (fused_moe.py:882-915): softmax, top-k and, with `renormalize`, the division
+void fused_topk(Tensor& topk_weights, Tensor& topk_ids, Tensor& token_expert_indices, const Tensor& gating_output,
+                bool renormalize) {
+  need_devs(topk_weights, topk_ids, token_expert_indices, gating_output);
+  route_check("topk_softmax", topk_weights, topk_ids, gating_output);
+  TORCH_CHECK(topk_ids.scalar_type() == at::kInt || topk_ids.scalar_type() == at::kLong,
+              "topk_softmax: topk_indices must be int32 or int64, got ", topk_ids.scalar_type());
+  TORCH_CHECK(is_i32(token_expert_indices) && token_expert_indices.sizes() == topk_weights.sizes(),
+              "topk_softmax: token_expert_indices must be contiguous int32 [num_tokens, topk]");
+  DevGuard g(gating_output.device());
+  check(vllm_amd_topk_softmax((float*)topk_weights.data_ptr(), topk_ids.data_ptr(),
+                              (int32_t*)token_expert_indices.data_ptr(), gating_output.data_ptr(), gating_output.size(0),
+                              (int)gating_output.size(1), (int)topk_weights.size(1), gating_output.stride(0),
+                              renormalize ? 1 : 0, dt(gating_output), topk_ids.scalar_type() == at::kLong ? 1 : 0,
+                              stream_of(gating_output)));
+}
+
+// csrc/moe/topk_softmax_kernels.cu (topk_softmax)
+void topk_softmax(Tensor& topk_weights, Tensor& topk_indices, Tensor& token_expert_indices, const Tensor& gating_output) {
+  fused_topk(topk_weights, topk_indices, token_expert_indices, gating_output, false);
+}
+
+// the reference's torch grouped_topk (fused_moe.py:920-975) as one op
+void grouped_topk(Tensor& topk_weights, Tensor& topk_ids, const Tensor& gating_output,
+                  const OptTensor& e_score_correction_bias, int64_t num_expert_group, int64_t topk_group,
+                  bool renormalize, const std::string& scoring_func) {
+  need_devs(topk_weights, topk_ids, gating_output, e_score_correction_bias);
+  route_check("grouped_topk", topk_weights, topk_ids, gating_output);
+  TORCH_CHECK(is_i32(topk_ids), "grouped_topk: topk_ids must be int32, got ", topk_ids.scalar_type());
+  TORCH_CHECK(scoring_func == "softmax" || scoring_func == "sigmoid", "Unsupported scoring function: ", scoring_func);
+  TORCH_CHECK(!e_score_correction_bias.has_value() ||
+                  (e_score_correction_bias->scalar_type() == at::kFloat && e_score_correction_bias->is_contiguous() &&
+                   e_score_correction_bias->numel() == gating_output.size(1)),
+              "grouped_topk: e_score_correction_bias must be contiguous float32 with one entry per expert");
+  TORCH_CHECK(num_expert_group >= INT32_MIN && num_expert_group <= INT32_MAX && topk_group >= INT32_MIN &&
+                  topk_group <= INT32_MAX, "grouped_topk: num_expert_group / topk_group out of range");
+  DevGuard g(gating_output.device());
+  check(vllm_amd_grouped_topk((float*)topk_weights.data_ptr(), (int32_t*)topk_ids.data_ptr(), gating_output.data_ptr(),
+                              fptr(e_score_correction_bias), gating_output.size(0), (int)gating_output.size(1),
+                              (int)topk_weights.size(1), (int)num_expert_group, (int)topk_group,
+                              scoring_func == "sigmoid" ? VLLM_AMD_SCORE_SIGMOID : VLLM_AMD_SCORE_SOFTMAX,
+                              renormalize ? 1 : 0, gating_output.stride(0), dt(gating_output), stream_of(gating_output)));
+}
+
 // silu_and_mul + per_token_group_fp8_quant (group 128) in one pass; input [rows, 2 d]
 void silu_and_mul_group_quant(Tensor& output_q, Tensor& output_s, const Tensor& input) {
   need_devs(output_q, output_s, input);
@@ -685,6 +739,21 @@ void register_all() {
         "                     Tensor! experts_ids,"
         "                     Tensor! num_tokens_post_pad) -> ()",
         &moe_align_block_size);
+  // csrc/moe/torch_bindings.cpp:6-9
+  mo.op("topk_softmax",
+        "topk_softmax(Tensor! topk_weights, Tensor! topk_indices, Tensor! "
+        "token_expert_indices, Tensor gating_output) -> ()",
+        &topk_softmax);
+  // no reference counterparts: fused_topk renormalises in torch after its op, grouped_topk is torch code there
+  mo.op("fused_topk",
+        "fused_topk(Tensor! topk_weights, Tensor! topk_ids, Tensor! token_expert_indices, Tensor gating_output,"
+        " bool renormalize) -> ()",
+        &fused_topk);
+  mo.op("grouped_topk",
+        "grouped_topk(Tensor! topk_weights, Tensor! topk_ids, Tensor gating_output,"
+        " Tensor? e_score_correction_bias, int num_expert_group, int topk_group, bool renormalize,"
+        " str scoring_func) -> ()",
+        &grouped_topk);
 
   Registrar k = open_ns("_C_cache_ops");
   k.op("reshape_and_cache",

@@ -1,6 +1,14 @@
-"""Fused MoE experts over block-scaled fp8 weights, with the names and arguments of the
-reference's ``vllm/model_executor/layers/fused_moe/fused_moe.py`` (fused_experts :1253-1346,
-fused_experts_impl :1349-1563, invoke_fused_moe_kernel :478-640).
+"""Fused MoE over block-scaled fp8 weights, routing included, with the names and arguments of the
+reference's ``vllm/model_executor/layers/fused_moe/fused_moe.py`` (fused_topk :882-915, grouped_topk
+:920-975, fused_experts :1253-1346, fused_experts_impl :1349-1563, invoke_fused_moe_kernel :478-640,
+fused_moe :1566-1689).
+
+Routing: ``fused_topk`` (softmax, top-k, optional renormalisation) and ``grouped_topk`` (softmax or
+sigmoid scores, optional correction bias, group-limited top-k) are ONE launch each of the routing
+kernel of libvllm_amd.so (csrc/moe_routing.hip), which reads the logits in their own dtype and scores
+them in fp32: no torch arithmetic, no host synchronisation.  Ties go to the lower expert / group
+index and the ids come in descending order of the selecting score (the reference asks torch.topk
+for ``sorted=False``).  ``fused_moe`` is routing followed by ``fused_experts``.
 
 Supported: ``use_fp8_w8a8=True`` with ``block_shape == [128, 128]``, silu with mul, dynamic
 activation scales, bf16 / f16 hidden states.  One layer is five launches and a sum, all HIP
@@ -11,10 +19,10 @@ synchronisation (graph-capturable):
   -> silu_and_mul_group_quant -> moe_block_fp8_gemm (w2, routed weights) -> moe_sum
 
 Anything else raises NotImplementedError naming the argument: there is no eager or Triton
-fallback.  Routing (fused_topk / grouped_topk) is the caller's: it passes topk_weights / topk_ids."""
+fallback."""
 from __future__ import annotations
 
-from typing import Any, Optional
+from typing import Any, Callable, Optional
 
 import torch
 
@@ -33,6 +41,52 @@ def _block_size_m(num_tokens: int, top_k: int, num_experts: int) -> int:
     # faster than 64 from 1 to 256 tokens, 64 is 1.06 - 1.32 x faster at 4096 tokens; the crossover
     # itself (between 256 and 4096 tokens) is not measured, the rule puts it at 512.
     return 16 if num_tokens * top_k <= 16 * num_experts else 64
+
+
+def _gating_2d(name: str, hidden_states: torch.Tensor, gating_output: torch.Tensor) -> None:
+    assert hidden_states.size(0) == gating_output.size(0), "Number of tokens mismatch"
+    if gating_output.dim() != 2 or (gating_output.size(1) > 1 and gating_output.stride(1) != 1):
+        raise NotImplementedError(f"{name}: gating_output must be [num_tokens, num_experts] with contiguous experts")
+    if gating_output.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"{name}: gating_output dtype {gating_output.dtype} is not implemented")
+
+
+def fused_topk(hidden_states: torch.Tensor, gating_output: torch.Tensor, topk: int, renormalize: bool,
+               indices_type: Optional[torch.dtype] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The ``topk`` largest softmax probabilities of every row of ``gating_output`` (fp32, bf16 or f16; no fp32
+    copy is made), divided by their sum with ``renormalize``: fp32 weights, ids of ``indices_type`` (int32 by
+    default, or int64) and token_expert_indices[t, k] = k * num_tokens + t, all [num_tokens, topk]."""
+    _gating_2d("fused_topk", hidden_states, gating_output)
+    if indices_type not in (None, torch.int32, torch.int64):
+        raise NotImplementedError(f"fused_topk: indices_type {indices_type} is not implemented (int32 or int64)")
+    M, dev = hidden_states.size(0), hidden_states.device
+    topk_weights = torch.empty((M, topk), dtype=torch.float32, device=dev)
+    topk_ids = torch.empty((M, topk), dtype=torch.int32 if indices_type is None else indices_type, device=dev)
+    token_expert_indices = torch.empty((M, topk), dtype=torch.int32, device=dev)
+    ops.fused_topk(topk_weights, topk_ids, token_expert_indices, gating_output, renormalize)
+    return topk_weights, topk_ids, token_expert_indices
+
+
+def grouped_topk(hidden_states: torch.Tensor, gating_output: torch.Tensor, topk: int, renormalize: bool,
+                 num_expert_group: int = 0, topk_group: int = 0, scoring_func: str = "softmax",
+                 e_score_correction_bias: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """DeepSeek-V2 / V3 routing: scores = softmax or sigmoid of the logits; the experts are selected by
+    scores + ``e_score_correction_bias`` (fp32, one entry per expert) among the ``topk_group`` best of
+    ``num_expert_group`` groups, a group scoring the sum of its two best with a bias and its best without;
+    the weights are the unbiased scores of the selected experts, divided by their sum with ``renormalize``.
+    Returns fp32 weights and int32 ids, [num_tokens, topk]."""
+    _gating_2d("grouped_topk", hidden_states, gating_output)
+    if scoring_func not in ("softmax", "sigmoid"):
+        raise ValueError(f"Unsupported scoring function: {scoring_func}")
+    if e_score_correction_bias is not None and e_score_correction_bias.dtype != torch.float32:
+        raise NotImplementedError(
+            f"grouped_topk: e_score_correction_bias dtype {e_score_correction_bias.dtype} is not implemented (float32)")
+    M, dev = hidden_states.size(0), hidden_states.device
+    topk_weights = torch.empty((M, topk), dtype=torch.float32, device=dev)
+    topk_ids = torch.empty((M, topk), dtype=torch.int32, device=dev)
+    ops.grouped_topk(topk_weights, topk_ids, gating_output, e_score_correction_bias, num_expert_group, topk_group,
+                     renormalize, scoring_func)
+    return topk_weights, topk_ids
 
 
 def invoke_fused_moe_kernel(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor,
@@ -154,3 +208,34 @@ def fused_experts(hidden_states: torch.Tensor, w1: torch.Tensor, w2: torch.Tenso
                                 block_shape=block_shape)
         ops.moe_sum(cache3, out[begin:end])
     return out
+
+
+def fused_moe(hidden_states: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, gating_output: torch.Tensor,
+              topk: int, renormalize: bool, inplace: bool = False, activation: str = "silu",
+              is_act_and_mul: bool = True, use_grouped_topk: bool = False,
+              num_expert_group: Optional[int] = None, topk_group: Optional[int] = None,
+              custom_routing_function: Optional[Callable] = None, use_fp8_w8a8: bool = False,
+              use_int8_w8a8: bool = False, use_int8_w8a16: bool = False, use_int4_w4a16: bool = False,
+              use_mxfp4_w4a4: bool = False, per_channel_quant: bool = False, global_num_experts: int = -1,
+              expert_map: Optional[torch.Tensor] = None, w1_scale: Optional[torch.Tensor] = None,
+              w2_scale: Optional[torch.Tensor] = None, w1_zp: Optional[torch.Tensor] = None,
+              w2_zp: Optional[torch.Tensor] = None, a1_scale: Optional[torch.Tensor] = None,
+              a2_scale: Optional[torch.Tensor] = None, block_shape: Optional[list[int]] = None) -> torch.Tensor:
+    """A whole MoE layer: routing of ``gating_output`` [M, E] (``grouped_topk`` with ``use_grouped_topk``, else
+    ``custom_routing_function(hidden_states, gating_output, topk, renormalize)`` when given, else ``fused_topk``),
+    then ``fused_experts`` with the remaining arguments."""
+    if use_grouped_topk:
+        assert num_expert_group is not None and topk_group is not None
+        topk_weights, topk_ids = grouped_topk(hidden_states, gating_output, topk, renormalize, num_expert_group,
+                                              topk_group)
+    elif custom_routing_function is None:
+        topk_weights, topk_ids, _ = fused_topk(hidden_states, gating_output, topk, renormalize)
+    else:
+        topk_weights, topk_ids = custom_routing_function(hidden_states, gating_output, topk, renormalize)
+    return fused_experts(hidden_states, w1, w2, topk_weights, topk_ids, inplace=inplace, activation=activation,
+                         is_act_and_mul=is_act_and_mul, use_fp8_w8a8=use_fp8_w8a8, use_int8_w8a8=use_int8_w8a8,
+                         use_int8_w8a16=use_int8_w8a16, use_int4_w4a16=use_int4_w4a16,
+                         use_mxfp4_w4a4=use_mxfp4_w4a4, per_channel_quant=per_channel_quant,
+                         global_num_experts=global_num_experts, expert_map=expert_map, w1_scale=w1_scale,
+                         w2_scale=w2_scale, w1_zp=w1_zp, w2_zp=w2_zp, a1_scale=a1_scale, a2_scale=a2_scale,
+                         block_shape=block_shape)
