@@ -362,6 +362,53 @@ int vllm_amd_moe_sum(void* out, const void* input, int64_t num_tokens, int top_k
                      int dtype, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Fused MoE experts over MXFP4 weights and activations (csrc/moe_mxfp4.hip)  */
+/* MXFP4 (OCP microscaling): e2m1 codes, two per byte (element 2j in the low  */
+/* nibble of byte j, sign in the nibble's top bit, magnitudes 0 .5 1 1.5 2 3  */
+/* 4 6), and one e8m0 scale byte (2^(byte - 127)) per 32 consecutive values.  */
+/* ------------------------------------------------------------------------- */
+
+/* No counterpart in the reference (its quantiser raises on gfx95, fused_moe/utils.py:172-175); the
+ * arithmetic is the "even" mode of its emulation (tests/quantization/reference_mxfp4.py).
+ * input: [num_rows, K] f16 / bf16, K contiguous, row stride row_stride elements (a multiple of 8);
+ * out_q: uint8 [num_rows, K/2] contiguous; out_s: uint8 [num_rows, K/32] contiguous.  Per 32-block:
+ * amax = f 2^e with f in [1, 2), e + 1 if f >= 1.75; out_s = clamp(e - 2 + 127, 0, 254), 0 for an
+ * all-zero block; out_q = x / 2^(out_s - 127) rounded to nearest-even onto the e2m1 grid, saturating
+ * at +-6, sign kept.  K % 32 == 0 (else VLLM_AMD_EUNSUPPORTED). */
+int vllm_amd_mxfp4_quant(void* out_q, void* out_s, const void* input, int64_t num_rows, int K,
+                         int64_t row_stride, int dtype, void* stream);
+
+/* The same quantiser on v = T(T(silu(x)) * y) as silu_and_mul rounds it, computed in registers from
+ * input [num_rows, 2 d] f16 / bf16 contiguous: out_q uint8 [num_rows, d/2], out_s uint8
+ * [num_rows, d/32], both contiguous.  d % 32 == 0. */
+int vllm_amd_silu_and_mul_mxfp4_quant(void* out_q, void* out_s, const void* input, int64_t num_rows,
+                                      int d, int dtype, void* stream);
+
+/* The grouped GEMM of fused_experts(use_mxfp4_w4a4=True).  The contract of vllm_amd_moe_blockwise_gemm
+ * over MXFP4 operands: for every i < *num_tokens_post_padded with t = sorted_token_ids[i] <
+ * num_valid_tokens and e = expert_ids[i / block_size_m]:
+ *   c[t, n] = ((topk_weights[t] if mul_routed_weight) * sum_k a[t / top_k, k] b[e, n, k]).to(out_dtype)
+ * over the dequantised values, accumulated in fp32 (the block scales are applied by the MFMA), the
+ * routed weight applied to the fp32 sum before the single rounding; e outside [0, num_experts) stores
+ * zeros; entries t >= num_valid_tokens are padding and store nothing; rows of c named by no entry are
+ * left as they are.
+ * a: codes [num_valid_tokens / top_k, K/2], row stride lda bytes; a_scales: e8m0 [rows, K/32], row
+ * stride as_stride_m; b: codes [E, N, K/2] with byte strides b_stride_e / b_stride_n; b_scales: e8m0
+ * [E, N, K/32] with strides bs_stride_e / bs_stride_n; the K axis of all four is contiguous.
+ * c, the id tensors, max_num_tokens_padded and topk_weights as for vllm_amd_moe_blockwise_gemm.
+ * K % 128 == 0 (else VLLM_AMD_EUNSUPPORTED), N arbitrary, block_size_m 16 or 64; lda and the code
+ * strides >= K/2 and multiples of 16, the scale strides >= K/32 and multiples of 4.  No workspace,
+ * nothing synchronised. */
+int vllm_amd_moe_mxfp4_gemm(void* c, const void* a, const void* b, const void* a_scales,
+                            const void* b_scales, const int32_t* sorted_token_ids,
+                            const int32_t* expert_ids, const int32_t* num_tokens_post_padded,
+                            const float* topk_weights, int num_valid_tokens, int top_k,
+                            int mul_routed_weight, int block_size_m, int max_num_tokens_padded,
+                            int num_experts, int N, int K, int64_t lda, int64_t b_stride_e,
+                            int64_t b_stride_n, int64_t ldc, int64_t as_stride_m, int64_t bs_stride_e,
+                            int64_t bs_stride_n, int out_dtype, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* MoE routing (csrc/moe_routing.hip): one launch per call, nothing allocated */
 /* or synchronised.  Ties go to the lower expert (and group) index; ids come  */
 /* in descending order of the selecting score, are distinct and lie in        */
@@ -700,8 +747,9 @@ int vllm_amd_ar_free_shared(void* ptr);
 /*   "mm_block_kernel": form of scaled_mm_blockwise: 0 = by M (streaming kernel */
 /*                 up to M 64, tile kernel above), 1 = tile kernel always,      */
 /*                 2 / 3 = its 128-row / 256-row form always                    */
-/*   "moe_ks":     waves per 16-column strip of moe_blockwise_gemm: 0 = by N    */
-/*                 and K (default), 8 = one strip per workgroup, 2 = four       */
+/*   "moe_ks":     waves per 16-column strip of moe_blockwise_gemm and          */
+/*                 moe_mxfp4_gemm: 0 = by N and K (default), 8 = one strip per  */
+/*                 workgroup, 2 = four                                          */
 /* ------------------------------------------------------------------------- */
 int vllm_amd_set_tuning(const char* key, int value);
 /* current value of "pa_balance" / "mm_kernel" / "mm_splitk" (the torch layer asks before it allocates) */

@@ -10,7 +10,13 @@ so every call streams them.  Yardstick, timed in the same process and alternated
 per-expert loop of cutlass_scaled_mm calls on the same data (gather of the expert's rows, block-scaled GEMM,
 scatter), with the row lists prepared on the host beforehand and the loop captured in a graph too, so its
 launch overhead is NOT counted against it.  Then "moe_ks" 8 against 2 for both GEMMs, block_size_m 16 against
-64, and the whole fused_experts call."""
+64, and the whole fused_experts call.
+
+    python tools/bench_moe.py --mxfp4 [--out FILE] [--tokens 1,16,64,256] [--inter 2048,256] [--iters 4]
+
+The MXFP4 (w4a4) path against the fp8 block-scaled path on the same shapes, alternated in the same process: per
+GEMM and for the whole fused_experts call, device time by graph replay and TB/s over the touched experts' weight
+bytes (codes and scales), and "moe_ks" 8 against 2 for the MXFP4 GEMM."""
 import argparse
 import os
 import sys
@@ -30,7 +36,10 @@ def main():
     ap.add_argument("--inter", default="2048,256")
     ap.add_argument("--iters", type=int, default=4)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mxfp4", action="store_true", help="MXFP4 (w4a4) against block-scaled fp8")
     a = ap.parse_args()
+    if a.mxfp4 and a.tokens == ap.get_default("tokens"):
+        a.tokens = "1,16,64,256"
     if not torch.cuda.is_available():
         print("bench_moe: no GPU", file=sys.stderr)
         return 2
@@ -55,6 +64,8 @@ def main():
         t = [bench.time_gpu_graph(f, iters) * 1e6 for f in (old, new, old, new)]
         return t[1], t[3], t[0], t[2]
 
+    if a.mxfp4:
+        return mxfp4_mode(a, dev, emit, fp8_rand, time_pair)
     emit(f"# E {E}, top-k {TOPK}, hidden {H}; us per call (two alternated rounds); TB/s = touched experts' weight bytes / "
          f"time, share of the {bench.HBM_PEAK_GBPS / 1000:.0f} TB/s HBM peak")
     for inter in (int(x) for x in a.inter.split(",")):
@@ -108,6 +119,63 @@ def main():
             emit(f"  I {inter:5d} tokens {tokens:5d} fused_experts (quant, align, w1, act + quant, w2, sum): {t:9.1f} us, "
                  f"{allb / t / 1e6:6.2f} TB/s over the touched weights")
         del w1, w2
+        torch.cuda.empty_cache()
+    return 0
+
+
+def mxfp4_mode(a, dev, emit, fp8_rand, time_pair):
+    from vllm_amd import _custom_ops as ops, _lib
+    from vllm_amd.model_executor.layers.fused_moe import fused_experts, moe_align_block_size
+    from vllm_amd.model_executor.layers.fused_moe.fused_moe import _block_size_m
+    u8 = lambda lo, hi, *shape: torch.randint(lo, hi, shape, device=dev, dtype=torch.uint8)
+    emit(f"# E {E}, top-k {TOPK}, hidden {H}; MXFP4 (w4a4) against block-scaled fp8, us per call (two alternated rounds "
+         f"each); TB/s = touched experts' weight bytes (codes + scales) / time, peak {bench.HBM_PEAK_GBPS / 1000:.0f} TB/s")
+    for inter in (int(x) for x in a.inter.split(",")):
+        f8 = dict(w1=fp8_rand(E, 2 * inter, H), w2=fp8_rand(E, H, inter),
+                  s1=torch.rand((E, 2 * inter // 128, H // 128), device=dev) * 1e-2,
+                  s2=torch.rand((E, H // 128, inter // 128), device=dev) * 1e-2)
+        mx = dict(w1=u8(0, 256, E, 2 * inter, H // 2), w2=u8(0, 256, E, H, inter // 2),     # all 16 codes
+                  s1=u8(118, 122, E, 2 * inter, H // 32), s2=u8(118, 122, E, H, inter // 32))
+        for tokens in (int(x) for x in a.tokens.split(",")):
+            g = torch.Generator(device=dev).manual_seed(tokens)
+            topk_w, ids = torch.randn((tokens, E), device=dev, generator=g).softmax(-1).topk(TOPK, dim=-1)
+            ids = ids.to(torch.int32)
+            touched, slots = ids.unique().numel(), tokens * TOPK
+            x = torch.randn((tokens, H), device=dev, dtype=torch.bfloat16) / 10
+            tw = topk_w.reshape(-1).contiguous()
+            bm = _block_size_m(tokens, TOPK, E)
+            al = moe_align_block_size(ids, bm, E)
+            for name, top_k, a_rows in (("w1", TOPK, tokens), ("w2", 1, slots)):
+                N, K = f8[name].shape[1], f8[name].shape[2]
+                c = torch.zeros((slots, N), dtype=torch.bfloat16, device=dev)
+                a8, As8 = fp8_rand(a_rows, K), torch.rand((a_rows, K // 128), device=dev) * 1e-2
+                a4, As4 = u8(0, 256, a_rows, K // 2), u8(125, 129, a_rows, K // 32)
+                w8, ws8, w4, ws4 = f8[name], f8["s" + name[1]], mx[name], mx["s" + name[1]]
+                fp8 = lambda: ops.moe_block_fp8_gemm(c, a8, w8, As8, ws8, tw, al[0], al[1], al[2], True, top_k, bm)
+                mx4 = lambda: ops.moe_mxfp4_gemm(c, a4, w4, As4, ws4, tw, al[0], al[1], al[2], True, top_k, bm)
+                n1, n2, o1, o2 = time_pair(mx4, fp8, a.iters)
+                tn, to = min(n1, n2), min(o1, o2)
+                b4, b8 = touched * N * (K // 2 + K // 32), touched * N * K
+                emit(f"  I {inter:5d} tokens {tokens:4d} {name} N {N:5d} K {K:5d} bm {bm:2d} touched {touched:3d} | mxfp4 {n1:8.1f} "
+                     f"{n2:8.1f} ({b4 / tn / 1e6:5.2f} TB/s) | fp8 {o1:8.1f} {o2:8.1f} ({b8 / to / 1e6:5.2f} TB/s) | "
+                     f"fp8 / mxfp4 time {to / tn:5.2f}, bytes {b8 / b4:4.2f}")
+                t = []
+                for ks in (8, 2) * 2:
+                    _lib.set_tuning("moe_ks", ks)
+                    t.append(bench.time_gpu_graph(mx4, a.iters) * 1e6)
+                _lib.set_tuning("moe_ks", 0)
+                emit(f"      mxfp4 moe_ks 8: {t[0]:8.1f} {t[2]:8.1f}  moe_ks 2: {t[1]:8.1f} {t[3]:8.1f}")
+            full8 = lambda: fused_experts(x, f8["w1"], f8["w2"], topk_w, ids, use_fp8_w8a8=True, w1_scale=f8["s1"],
+                                          w2_scale=f8["s2"], block_shape=[128, 128])
+            full4 = lambda: fused_experts(x, mx["w1"], mx["w2"], topk_w, ids, use_mxfp4_w4a4=True, w1_scale=mx["s1"],
+                                          w2_scale=mx["s2"])
+            n1, n2, o1, o2 = time_pair(full4, full8, a.iters)
+            tn, to = min(n1, n2), min(o1, o2)
+            b8 = touched * 3 * inter * H
+            b4 = b8 // 2 + b8 // 32
+            emit(f"  I {inter:5d} tokens {tokens:4d} fused_experts | mxfp4 {n1:8.1f} {n2:8.1f} ({b4 / tn / 1e6:5.2f} TB/s) | fp8 "
+                 f"{o1:8.1f} {o2:8.1f} ({b8 / to / 1e6:5.2f} TB/s) | fp8 / mxfp4 time {to / tn:5.2f}, bytes {b8 / b4:4.2f}")
+        del f8, mx
         torch.cuda.empty_cache()
     return 0
 

@@ -310,3 +310,29 @@ def silu_and_mul_group_quant(output_q: torch.Tensor, output_s: torch.Tensor,
     """silu_and_mul of ``input`` [rows, 2 d], quantised in 128-wide groups: fp8 ``output_q``
     [rows, d] and fp32 ``output_s`` [rows, d / 128] (any strides)."""
     torch.ops._C.silu_and_mul_group_quant(output_q, output_s, input)
+
+
+# ---- MXFP4 (w4a4) experts: no reference counterparts (its quantiser raises on gfx95 and its GEMM
+# ---- runs on weights dequantised to bf16, quark_moe.py:284-291) ------------------------------------
+def mxfp4_quant(output_q: torch.Tensor, output_s: torch.Tensor, input: torch.Tensor) -> None:
+    """``input`` [rows, K] bf16 / f16 (K contiguous, any row stride) as MXFP4: uint8 e2m1 codes
+    ``output_q`` [rows, K / 2] (element 2 j in the low nibble of byte j) and uint8 e8m0 scales
+    ``output_s`` [rows, K / 32]; round-to-nearest-even, K % 32 == 0."""
+    torch.ops._C.mxfp4_quant(output_q, output_s, input)
+
+
+def silu_and_mul_mxfp4_quant(output_q: torch.Tensor, output_s: torch.Tensor, input: torch.Tensor) -> None:
+    """silu_and_mul of ``input`` [rows, 2 d] quantised as by ``mxfp4_quant``: ``output_q`` [rows, d / 2],
+    ``output_s`` [rows, d / 32]."""
+    torch.ops._C.silu_and_mul_mxfp4_quant(output_q, output_s, input)
+
+
+def moe_mxfp4_gemm(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor, a_scales: torch.Tensor,
+                   b_scales: torch.Tensor, topk_weights: Optional[torch.Tensor],
+                   sorted_token_ids: torch.Tensor, expert_ids: torch.Tensor,
+                   num_tokens_post_padded: torch.Tensor, mul_routed_weight: bool, top_k: int,
+                   block_size_m: int) -> None:
+    """``moe_block_fp8_gemm`` over MXFP4 operands: a [rows, K / 2] and b [E, N, K / 2] uint8 codes, a_scales
+    [rows, K / 32] and b_scales [E, N, K / 32] uint8 e8m0; K % 128 == 0."""
+    torch.ops._C.moe_mxfp4_gemm(c, a, b, a_scales, b_scales, topk_weights, sorted_token_ids, expert_ids,
+                                num_tokens_post_padded, mul_routed_weight, top_k, block_size_m)

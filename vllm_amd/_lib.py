@@ -62,6 +62,11 @@ SIGNATURES = {
     "vllm_amd_moe_align_block_size": [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp],
     "vllm_amd_silu_and_mul_group_quant": [_vp, _vp, _vp, _i64, _i, _i64, _i64, _i, _vp],
     "vllm_amd_moe_sum": [_vp, _vp, _i64, _i, _i, _i, _vp],
+    "vllm_amd_mxfp4_quant": [_vp, _vp, _vp, _i64, _i, _i64, _i, _vp],
+    "vllm_amd_silu_and_mul_mxfp4_quant": [_vp, _vp, _vp, _i64, _i, _i, _vp],
+    "vllm_amd_moe_mxfp4_gemm": [
+        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64,
+        _i64, _i64, _i64, _i, _vp],
     "vllm_amd_topk_softmax": [_vp, _vp, _vp, _vp, _i64, _i, _i, _i64, _i, _i, _i, _vp],
     "vllm_amd_grouped_topk": [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i64, _i, _vp],
     "vllm_amd_set_workspace": [_vp, _i64, _vp],

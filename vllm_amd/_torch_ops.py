@@ -122,6 +122,19 @@ grouped_topk = torch.ops._moe_C.grouped_topk
 #: ops -- the reference's grouped GEMM is a Triton kernel
 moe_block_fp8_gemm = torch.ops._C.moe_block_fp8_gemm
 silu_and_mul_group_quant = torch.ops._C.silu_and_mul_group_quant
+#: the MXFP4 (w4a4) expert path (csrc/moe_mxfp4.hip): activation quantiser, its fusion with silu_and_mul
+#: and the grouped GEMM on the fp4 scaled MFMA; not reference ops either
+mxfp4_quant = torch.ops._C.mxfp4_quant
+silu_and_mul_mxfp4_quant = torch.ops._C.silu_and_mul_mxfp4_quant
+moe_mxfp4_gemm = torch.ops._C.moe_mxfp4_gemm
+
+
+def _no_output(*args, **kwargs) -> None:
+    """Fake (meta) implementation of an op that only writes into its ``Tensor!`` arguments."""
+
+
+for _name in ("mxfp4_quant", "silu_and_mul_mxfp4_quant", "moe_mxfp4_gemm"):
+    torch.library.register_fake(f"_C::{_name}")(_no_output)
 #: device-side BlockTable.compute_slot_mapping (vllm/v1/worker/block_table.py:84-99); not a
 #: reference op -- the reference does this with numpy on the host
 compute_slot_mapping = torch.ops._vllm_amd_C.compute_slot_mapping

@@ -541,6 +541,91 @@ void silu_and_mul_group_quant(Tensor& output_q, Tensor& output_s, const Tensor& 
                                           stream_of(input)));
 }
 
+// ---- fused MoE over MXFP4 weights and activations (csrc/moe_mxfp4.hip) -----------------------------
+inline bool is_u8(const Tensor& t) { return t.scalar_type() == at::kByte; }
+
+// codes [rows, K / 2] and e8m0 scale bytes [rows, K / 32] of a 16-bit [rows, K]
+void mxfp4_out_check(const char* op, const Tensor& q, const Tensor& s, int64_t rows, int64_t d) {
+  TORCH_CHECK(d % 32 == 0, op, ": row length ", d, " is not a multiple of the 32-wide MX block");
+  TORCH_CHECK(is_u8(q) && is_u8(s) && q.is_contiguous() && s.is_contiguous() && q.dim() == 2 && s.dim() == 2 &&
+                  q.size(0) == rows && q.size(1) == d / 2 && s.size(0) == rows && s.size(1) == d / 32,
+              op, ": contiguous uint8 output_q [rows, d / 2] and output_s [rows, d / 32] required");
+}
+
+void mxfp4_quant(Tensor& output_q, Tensor& output_s, const Tensor& input) {
+  need_devs(output_q, output_s, input);
+  TORCH_CHECK(input.dim() == 2 && (input.size(1) <= 1 || input.stride(1) == 1),
+              "mxfp4_quant: input [rows, K] with K contiguous required");
+  TORCH_CHECK(input.scalar_type() == at::kBFloat16 || input.scalar_type() == at::kHalf,
+              "mxfp4_quant: input must be bfloat16 or float16, got ", input.scalar_type());
+  mxfp4_out_check("mxfp4_quant", output_q, output_s, input.size(0), input.size(1));
+  DevGuard g(input.device());
+  check(vllm_amd_mxfp4_quant(output_q.data_ptr(), output_s.data_ptr(), input.data_ptr(), input.size(0),
+                             (int)input.size(1), input.size(0) > 1 ? input.stride(0) : input.size(1), dt(input),
+                             stream_of(input)));
+}
+
+// silu_and_mul + the MXFP4 quantiser in one pass; input [rows, 2 d]
+void silu_and_mul_mxfp4_quant(Tensor& output_q, Tensor& output_s, const Tensor& input) {
+  need_devs(output_q, output_s, input);
+  TORCH_CHECK(input.dim() == 2 && input.is_contiguous() && input.size(1) % 2 == 0,
+              "silu_and_mul_mxfp4_quant: contiguous input [rows, 2 * d] required");
+  TORCH_CHECK(input.scalar_type() == at::kBFloat16 || input.scalar_type() == at::kHalf,
+              "silu_and_mul_mxfp4_quant: input must be bfloat16 or float16, got ", input.scalar_type());
+  mxfp4_out_check("silu_and_mul_mxfp4_quant", output_q, output_s, input.size(0), input.size(1) / 2);
+  DevGuard g(input.device());
+  check(vllm_amd_silu_and_mul_mxfp4_quant(output_q.data_ptr(), output_s.data_ptr(), input.data_ptr(), input.size(0),
+                                          (int)(input.size(1) / 2), dt(input), stream_of(input)));
+}
+
+// The grouped GEMM of fused_experts(use_mxfp4_w4a4=True): the arguments of moe_block_fp8_gemm with
+// a [rows, K / 2] and b [E, N, K / 2] uint8 codes, a_scales [rows, K / 32] and b_scales [E, N, K / 32] uint8 e8m0.
+void moe_mxfp4_gemm(Tensor& c, const Tensor& a, const Tensor& b, const Tensor& a_scales, const Tensor& b_scales,
+                    const OptTensor& topk_weights, const Tensor& sorted_token_ids, const Tensor& expert_ids,
+                    const Tensor& num_tokens_post_padded, bool mul_routed_weight, int64_t top_k,
+                    int64_t block_size_m) {
+  need_devs(c, a, b, a_scales, b_scales, topk_weights, sorted_token_ids, expert_ids, num_tokens_post_padded);
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 3 && (c.dim() == 2 || c.dim() == 3) && a_scales.dim() == 2 &&
+                  b_scales.dim() == 3,
+              "moe_mxfp4_gemm: a [rows, K/2], b [E, N, K/2], c [rows * top_k, N], a_scales 2-D, b_scales 3-D");
+  const int64_t K = a.size(1) * 2, E = b.size(0), N = b.size(1);
+  TORCH_CHECK(c.size(-1) == N && c.stride(-1) == 1 && (c.dim() == 2 || c.stride(0) == c.size(1) * c.stride(1)),
+              "moe_mxfp4_gemm: c must have N contiguous columns and evenly strided rows");
+  const int64_t nvt = N ? c.numel() / N : 0;
+  TORCH_CHECK(top_k >= 1 && a.size(0) * top_k == nvt, "moe_mxfp4_gemm: c rows == a rows * top_k");
+  TORCH_CHECK(is_u8(a) && is_u8(b) && is_u8(a_scales) && is_u8(b_scales),
+              "moe_mxfp4_gemm: uint8 codes and e8m0 scale bytes required");
+  TORCH_CHECK(b.size(2) * 2 == K && a.stride(1) == 1 && b.stride(2) == 1 && a_scales.stride(1) == 1 &&
+                  b_scales.stride(2) == 1,
+              "moe_mxfp4_gemm: K mismatch / K not contiguous");
+  TORCH_CHECK(c.scalar_type() == at::kBFloat16 || c.scalar_type() == at::kHalf,
+              "moe_mxfp4_gemm: c must be bfloat16 or float16, got ", c.scalar_type());
+  TORCH_CHECK(a_scales.size(0) == a.size(0) && a_scales.size(1) * 32 == K && b_scales.size(0) == E &&
+                  b_scales.size(1) == N && b_scales.size(2) * 32 == K,
+              "moe_mxfp4_gemm: a_scales [rows, K/32] and b_scales [E, N, K/32] required");
+  TORCH_CHECK(is_i32(sorted_token_ids) && is_i32(expert_ids) && is_i32(num_tokens_post_padded),
+              "moe_mxfp4_gemm: contiguous int32 sorted_token_ids / expert_ids / num_tokens_post_padded required");
+  TORCH_CHECK(block_size_m > 0, "moe_mxfp4_gemm: block_size_m > 0");
+  // the bound and its cap as in moe_block_fp8_gemm
+  const int64_t max_padded = std::min<int64_t>(sorted_token_ids.numel(), nvt * block_size_m);
+  TORCH_CHECK(sorted_token_ids.numel() >= nvt && max_padded < INT32_MAX &&
+                  expert_ids.numel() >= (max_padded + block_size_m - 1) / block_size_m &&
+                  num_tokens_post_padded.numel() >= 1,
+              "moe_mxfp4_gemm: sorted_token_ids holds fewer entries than c has rows, or expert_ids fewer than one "
+              "per block_size_m entries of it");
+  TORCH_CHECK(!mul_routed_weight || topk_weights.has_value(), "moe_mxfp4_gemm: mul_routed_weight needs topk_weights");
+  TORCH_CHECK(!topk_weights.has_value() || (topk_weights->scalar_type() == at::kFloat && topk_weights->is_contiguous() &&
+                                            topk_weights->numel() == nvt),
+              "moe_mxfp4_gemm: topk_weights must be contiguous float32 with one entry per row of c");
+  DevGuard g(a.device());
+  check(vllm_amd_moe_mxfp4_gemm(
+      c.data_ptr(), a.data_ptr(), b.data_ptr(), a_scales.data_ptr(), b_scales.data_ptr(),
+      (const int32_t*)sorted_token_ids.data_ptr(), (const int32_t*)expert_ids.data_ptr(),
+      (const int32_t*)num_tokens_post_padded.data_ptr(), fptr(topk_weights), (int)nvt, (int)top_k,
+      mul_routed_weight ? 1 : 0, (int)block_size_m, (int)max_padded, (int)E, (int)N, (int)K, a.stride(0), b.stride(0),
+      b.stride(1), c.stride(-2), a_scales.stride(0), b_scales.stride(0), b_scales.stride(1), dt(c), stream_of(a)));
+}
+
 void wvSplitKQ(const Tensor& in_a, const Tensor& in_b, Tensor& out_c, const Tensor& scale_a, const Tensor& scale_b,
                int64_t cu_count) {
   need_devs(in_a, in_b, out_c, scale_a, scale_b);
@@ -729,6 +814,16 @@ void register_all() {
   c.op("silu_and_mul_group_quant",
        "silu_and_mul_group_quant(Tensor! output_q, Tensor! output_s, Tensor input) -> ()",
        &silu_and_mul_group_quant);
+  // the MXFP4 (w4a4) path: no reference counterparts either (there the weights are dequantised to bf16)
+  c.op("mxfp4_quant", "mxfp4_quant(Tensor! output_q, Tensor! output_s, Tensor input) -> ()", &mxfp4_quant);
+  c.op("silu_and_mul_mxfp4_quant",
+       "silu_and_mul_mxfp4_quant(Tensor! output_q, Tensor! output_s, Tensor input) -> ()",
+       &silu_and_mul_mxfp4_quant);
+  c.op("moe_mxfp4_gemm",
+       "moe_mxfp4_gemm(Tensor! c, Tensor a, Tensor b, Tensor a_scales, Tensor b_scales,"
+       " Tensor? topk_weights, Tensor sorted_token_ids, Tensor expert_ids,"
+       " Tensor num_tokens_post_padded, bool mul_routed_weight, int top_k, int block_size_m) -> ()",
+       &moe_mxfp4_gemm);
 
   // csrc/moe/torch_bindings.cpp:13-22
   Registrar mo = open_ns("_moe_C");

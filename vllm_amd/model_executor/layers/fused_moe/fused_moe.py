@@ -10,13 +10,17 @@ them in fp32: no torch arithmetic, no host synchronisation.  Ties go to the lowe
 index and the ids come in descending order of the selecting score (the reference asks torch.topk
 for ``sorted=False``).  ``fused_moe`` is routing followed by ``fused_experts``.
 
-Supported: ``use_fp8_w8a8=True`` with ``block_shape == [128, 128]``, silu with mul, dynamic
-activation scales, bf16 / f16 hidden states.  One layer is five launches and a sum, all HIP
+Supported: ``use_fp8_w8a8=True`` with ``block_shape == [128, 128]``, or ``use_mxfp4_w4a4=True`` (OCP MXFP4
+weights AND activations, e8m0 scales per 32 values, on the fp4 scaled MFMA; csrc/moe_mxfp4.hip); silu with
+mul, dynamic activation scales, bf16 / f16 hidden states.  One layer is five launches and a sum, all HIP
 kernels of libvllm_amd.so, plus the zero fill of the second GEMM's output, with no host
 synchronisation (graph-capturable):
 
   per_token_group_fp8_quant -> moe_align_block_size -> moe_block_fp8_gemm (w1)
   -> silu_and_mul_group_quant -> moe_block_fp8_gemm (w2, routed weights) -> moe_sum
+
+  mxfp4_quant -> moe_align_block_size -> moe_mxfp4_gemm (w1)
+  -> silu_and_mul_mxfp4_quant -> moe_mxfp4_gemm (w2, routed weights) -> moe_sum
 
 Anything else raises NotImplementedError naming the argument: there is no eager or Triton
 fallback."""
@@ -141,17 +145,25 @@ def fused_experts(hidden_states: torch.Tensor, w1: torch.Tensor, w2: torch.Tenso
                   allow_cutlass_block_scaled_grouped_gemm: bool = False) -> torch.Tensor:
     """hidden_states [M, K]; w1 [E, 2 I, K] and w2 [E, K, I] fp8 e4m3 with w1_scale
     [E, ceil(2 I / 128), K / 128] and w2_scale [E, ceil(K / 128), I / 128]; topk_weights / topk_ids
-    [M, top_k].  Returns sum_k topk_weights[m, k] * expert_{topk_ids[m, k]}(hidden_states[m]), written
+    [M, top_k].  With ``use_mxfp4_w4a4``: w1 [E, 2 I, K / 2] and w2 [E, K, I / 2] uint8 (two e2m1 codes per
+    byte, the even element in the low nibble) with w1_scale [E, 2 I, K / 32] and w2_scale [E, K, I / 32]
+    uint8 e8m0, K and I multiples of 128, no ``block_shape``.
+    Returns sum_k topk_weights[m, k] * expert_{topk_ids[m, k]}(hidden_states[m]), written
     into ``hidden_states`` with ``inplace``.  A slot whose id is outside [0, global_num_experts) adds
     nothing; with ``expert_map`` (global -> local index, -1 = absent) w1 / w2 hold the local experts."""
     for name, flag in (("use_int8_w8a8", use_int8_w8a8), ("use_int8_w8a16", use_int8_w8a16),
-                       ("use_int4_w4a16", use_int4_w4a16), ("use_mxfp4_w4a4", use_mxfp4_w4a4),
-                       ("per_channel_quant", per_channel_quant)):
+                       ("use_int4_w4a16", use_int4_w4a16), ("per_channel_quant", per_channel_quant)):
         if flag:
             raise NotImplementedError(f"fused_experts: {name} is not implemented on gfx950")
-    if not use_fp8_w8a8:
-        raise NotImplementedError("fused_experts: only use_fp8_w8a8=True is implemented")
-    if block_shape is None or list(block_shape) != [128, 128]:
+    if use_mxfp4_w4a4:
+        if use_fp8_w8a8:
+            raise NotImplementedError("fused_experts: use_fp8_w8a8 cannot be combined with use_mxfp4_w4a4")
+        if block_shape is not None:
+            raise NotImplementedError("fused_experts: block_shape is not implemented with use_mxfp4_w4a4 "
+                                      "(MXFP4 scales are one per 32 values)")
+    elif not use_fp8_w8a8:
+        raise NotImplementedError("fused_experts: only use_fp8_w8a8=True and use_mxfp4_w4a4=True are implemented")
+    elif block_shape is None or list(block_shape) != [128, 128]:
         raise NotImplementedError("fused_experts: block_shape must be [128, 128]")
     if activation != "silu" or not is_act_and_mul:
         raise NotImplementedError(
@@ -163,7 +175,12 @@ def fused_experts(hidden_states: torch.Tensor, w1: torch.Tensor, w2: torch.Tenso
     if hidden_states.dtype not in (torch.bfloat16, torch.float16):
         raise NotImplementedError(f"fused_experts: hidden_states dtype {hidden_states.dtype} is not implemented")
     assert w1_scale is not None and w2_scale is not None, "block-scaled weights need their scales"
-    assert hidden_states.size(1) == w1.size(2), f"Hidden size mismatch {hidden_states.size(1)} != {w1.size(2)}"
+    pack = 2 if use_mxfp4_w4a4 else 1                     # values per weight byte
+    if use_mxfp4_w4a4 and (hidden_states.size(1) % 128 or w2.size(2) * 2 % 128):
+        raise NotImplementedError(f"fused_experts: use_mxfp4_w4a4 needs K = {hidden_states.size(1)} and I = "
+                                  f"{w2.size(2) * 2} to be multiples of 128")
+    assert hidden_states.size(1) == w1.size(2) * pack, \
+        f"Hidden size mismatch {hidden_states.size(1)} != {w1.size(2) * pack}"
     assert topk_weights.size() == topk_ids.size(), "topk shape mismatch"
     assert hidden_states.is_contiguous(), "Hidden_states must be contiguous"
     assert w1.stride(-1) == 1 and w2.stride(-1) == 1, "Stride of last dimension must be 1"
@@ -171,7 +188,7 @@ def fused_experts(hidden_states: torch.Tensor, w1: torch.Tensor, w2: torch.Tenso
     num_tokens = hidden_states.size(0)
     E, N, _ = w1.size()
     K = w2.size(1)
-    assert w2.size(2) * 2 == N, "w1 holds gate and up: [E, 2 I, K] against w2 [E, K, I]"
+    assert w2.size(2) * pack * 2 == N, "w1 holds gate and up: [E, 2 I, K] against w2 [E, K, I]"
     if global_num_experts == -1:
         global_num_experts = E
     top_k = topk_ids.size(1)
@@ -193,19 +210,31 @@ def fused_experts(hidden_states: torch.Tensor, w1: torch.Tensor, w2: torch.Tenso
         # zeros: a slot whose id is outside [0, global_num_experts) is in no expert's run, so neither GEMM
         # writes its row, and moe_sum must add nothing for it (cache1 / q2 rows of such slots are never read)
         cache3 = torch.zeros((m, top_k, K), device=dev, dtype=dtype)
-        q2 = torch.empty((m * top_k, N // 2), device=dev, dtype=ops.FP8_DTYPE)
-        s2 = torch.empty((m * top_k, N // 256), device=dev, dtype=torch.float32)
-
-        q1, s1 = per_token_group_quant_fp8(hidden_states[begin:end], 128)
-        sorted_ids, expert_ids, num_post = moe_align_block_size(ids, config["BLOCK_SIZE_M"],
-                                                                global_num_experts, expert_map)
-        invoke_fused_moe_kernel(q1, w1, cache1, s1, w1_scale, None, weights, sorted_ids, expert_ids, num_post,
-                                apply_router_weight_on_input, top_k, config, use_fp8_w8a8=True,
-                                block_shape=block_shape)
-        ops.silu_and_mul_group_quant(q2, s2, cache1)
-        invoke_fused_moe_kernel(q2, w2, cache3, s2, w2_scale, None, weights, sorted_ids, expert_ids, num_post,
-                                not apply_router_weight_on_input, 1, config, use_fp8_w8a8=True,
-                                block_shape=block_shape)
+        bm = config["BLOCK_SIZE_M"]
+        if use_mxfp4_w4a4:
+            q1 = torch.empty((m, K // 2), device=dev, dtype=torch.uint8)
+            s1 = torch.empty((m, K // 32), device=dev, dtype=torch.uint8)
+            q2 = torch.empty((m * top_k, N // 4), device=dev, dtype=torch.uint8)
+            s2 = torch.empty((m * top_k, N // 64), device=dev, dtype=torch.uint8)
+            ops.mxfp4_quant(q1, s1, hidden_states[begin:end])
+            sorted_ids, expert_ids, num_post = moe_align_block_size(ids, bm, global_num_experts, expert_map)
+            ops.moe_mxfp4_gemm(cache1, q1, w1, s1, w1_scale, weights.view(-1), sorted_ids, expert_ids, num_post,
+                               apply_router_weight_on_input, top_k, bm)
+            ops.silu_and_mul_mxfp4_quant(q2, s2, cache1)
+            ops.moe_mxfp4_gemm(cache3, q2, w2, s2, w2_scale, weights.view(-1), sorted_ids, expert_ids, num_post,
+                               not apply_router_weight_on_input, 1, bm)
+        else:
+            q2 = torch.empty((m * top_k, N // 2), device=dev, dtype=ops.FP8_DTYPE)
+            s2 = torch.empty((m * top_k, N // 256), device=dev, dtype=torch.float32)
+            q1, s1 = per_token_group_quant_fp8(hidden_states[begin:end], 128)
+            sorted_ids, expert_ids, num_post = moe_align_block_size(ids, bm, global_num_experts, expert_map)
+            invoke_fused_moe_kernel(q1, w1, cache1, s1, w1_scale, None, weights, sorted_ids, expert_ids, num_post,
+                                    apply_router_weight_on_input, top_k, config, use_fp8_w8a8=True,
+                                    block_shape=block_shape)
+            ops.silu_and_mul_group_quant(q2, s2, cache1)
+            invoke_fused_moe_kernel(q2, w2, cache3, s2, w2_scale, None, weights, sorted_ids, expert_ids, num_post,
+                                    not apply_router_weight_on_input, 1, config, use_fp8_w8a8=True,
+                                    block_shape=block_shape)
         ops.moe_sum(cache3, out[begin:end])
     return out
 
