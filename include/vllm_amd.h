@@ -319,7 +319,8 @@ int vllm_amd_scaled_mm_blockwise(void* out, const void* a, const void* b,
  * block_size_m entries of that length; num_tokens_post_padded: int32 [1], read on the device (the
  * grid is the host-side bound max_num_tokens_padded, which also caps the device-side count);
  * topk_weights: float [num_valid_tokens], may be NULL without
- * mul_routed_weight.  K % 128 == 0 (else VLLM_AMD_EUNSUPPORTED), N arbitrary, block_size_m 16 or 64;
+ * mul_routed_weight.  K % 128 == 0 (else VLLM_AMD_EUNSUPPORTED), N arbitrary, block_size_m 16, 64 or 128
+ * (16 / 64: the weight-streaming kernel for decode; 128: the LDS-staged 128 x 128 tile kernel for prefill);
  * lda and the weight strides >= K and multiples of 16.  No workspace, nothing synchronised. */
 int vllm_amd_moe_blockwise_gemm(void* c, const void* a, const void* b, const float* a_scales,
                                 const float* b_scales, const int32_t* sorted_token_ids,

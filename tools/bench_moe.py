@@ -16,7 +16,14 @@ launch overhead is NOT counted against it.  Then "moe_ks" 8 against 2 for both G
 
 The MXFP4 (w4a4) path against the fp8 block-scaled path on the same shapes, alternated in the same process: per
 GEMM and for the whole fused_experts call, device time by graph replay and TB/s over the touched experts' weight
-bytes (codes and scales), and "moe_ks" 8 against 2 for the MXFP4 GEMM."""
+bytes (codes and scales), and "moe_ks" 8 against 2 for the MXFP4 GEMM.
+
+    python tools/bench_moe.py --tile [--out FILE] [--tokens 256,512,1024,2048,4096,16384] [--inter 2048,256]
+
+Prefill: block_size_m 128 (the grouped tile kernel) against 64 (the weight-streaming kernel) for both GEMMs, and for
+the whole fused_experts call 128 against what _block_size_m picks without the tile kernel (16 or 64), alternated in
+the same process, two rounds each.  Achieved TFLOP/s from 2 * valid rows * N * K, and the share of the larger of the
+two lower bounds on the time: that work at the fp8 MFMA peak, or the touched experts' weight bytes at the HBM peak."""
 import argparse
 import os
 import sys
@@ -37,7 +44,10 @@ def main():
     ap.add_argument("--iters", type=int, default=4)
     ap.add_argument("--out", default=None)
     ap.add_argument("--mxfp4", action="store_true", help="MXFP4 (w4a4) against block-scaled fp8")
+    ap.add_argument("--tile", action="store_true", help="block_size_m 128 (tile kernel) against 64 at prefill sizes")
     a = ap.parse_args()
+    if a.tile and a.tokens == ap.get_default("tokens"):
+        a.tokens = "256,512,1024,2048,4096,16384"
     if a.mxfp4 and a.tokens == ap.get_default("tokens"):
         a.tokens = "1,16,64,256"
     if not torch.cuda.is_available():
@@ -66,6 +76,8 @@ def main():
 
     if a.mxfp4:
         return mxfp4_mode(a, dev, emit, fp8_rand, time_pair)
+    if a.tile:
+        return tile_mode(a, dev, emit, fp8_rand, time_pair)
     emit(f"# E {E}, top-k {TOPK}, hidden {H}; us per call (two alternated rounds); TB/s = touched experts' weight bytes / "
          f"time, share of the {bench.HBM_PEAK_GBPS / 1000:.0f} TB/s HBM peak")
     for inter in (int(x) for x in a.inter.split(",")):
@@ -99,7 +111,7 @@ def main():
                         src = r // top_k
                         o = ops.cutlass_scaled_mm(aq[src], w[e].t(), As[src], ws[e].t(), torch.bfloat16)
                         c[r] = o
-                bm = _block_size_m(tokens, TOPK, E)
+                bm = min(_block_size_m(tokens, TOPK, E), 64)   # the tile kernel (128) has its own mode: --tile
                 n1, n2, o1, o2 = time_pair(new_call(bm, aligned(bm)), loop, a.iters)
                 tn = min(n1, n2)
                 emit(f"  I {inter:5d} tokens {tokens:5d} {name} N {N:5d} K {K:5d} bm {bm:2d} touched {touched:3d} | grouped {n1:9.1f} "
@@ -118,6 +130,61 @@ def main():
             allb = touched * 3 * inter * H
             emit(f"  I {inter:5d} tokens {tokens:5d} fused_experts (quant, align, w1, act + quant, w2, sum): {t:9.1f} us, "
                  f"{allb / t / 1e6:6.2f} TB/s over the touched weights")
+        del w1, w2
+        torch.cuda.empty_cache()
+    return 0
+
+
+def tile_mode(a, dev, emit, fp8_rand, time_pair):
+    from vllm_amd import _custom_ops as ops
+    from vllm_amd.model_executor.layers.fused_moe import fused_experts, moe_align_block_size
+    fm = sys.modules[fused_experts.__module__]   # the module: the package exports a function of the same name
+    peak_f, peak_b = bench.FP8_DENSE_PEAK_TFLOPS * 1e12, bench.HBM_PEAK_GBPS * 1e9
+    emit(f"# E {E}, top-k {TOPK}, hidden {H}; block_size_m 128 (tile kernel) against 64 (streaming kernel), us per call, two "
+         f"alternated rounds each; TFLOP/s = 2 * valid rows * N * K / time of 128; bound = the larger of that work at "
+         f"{peak_f / 1e15:.0f} PFLOP/s (mfma) and the touched experts' weight bytes at {peak_b / 1e12:.0f} TB/s (hbm)")
+    for inter in (int(x) for x in a.inter.split(",")):
+        w1, w2 = fp8_rand(E, 2 * inter, H), fp8_rand(E, H, inter)
+        w1_s = torch.rand((E, 2 * inter // 128, H // 128), device=dev) * 1e-2
+        w2_s = torch.rand((E, H // 128, inter // 128), device=dev) * 1e-2
+        for tokens in (int(x) for x in a.tokens.split(",")):
+            g = torch.Generator(device=dev).manual_seed(tokens)
+            topk_w, ids = torch.randn((tokens, E), device=dev, generator=g).softmax(-1).topk(TOPK, dim=-1)
+            ids = ids.to(torch.int32)
+            touched, slots = ids.unique().numel(), tokens * TOPK
+            x = torch.randn((tokens, H), device=dev, dtype=torch.bfloat16) / 10
+            tw = topk_w.reshape(-1).contiguous()
+            al = {bm: moe_align_block_size(ids, bm, E) for bm in (64, 128)}
+            for name, w, ws, top_k, a_rows in (("w1", w1, w1_s, TOPK, tokens), ("w2", w2, w2_s, 1, slots)):
+                N, K = w.shape[1], w.shape[2]
+                aq, As = fp8_rand(a_rows, K), torch.rand((a_rows, K // 128), device=dev) * 1e-2
+                c = torch.zeros((slots, N), dtype=torch.bfloat16, device=dev)
+
+                def call(bm):
+                    s, e, p = al[bm]
+                    return lambda: ops.moe_block_fp8_gemm(c, aq, w, As, ws, tw, s, e, p, True, top_k, bm)
+                n1, n2, o1, o2 = time_pair(call(128), call(64), a.iters)
+                tn, flop = min(n1, n2) * 1e-6, 2.0 * slots * N * K
+                t_f, t_b = flop / peak_f, touched * N * K / peak_b
+                emit(f"  I {inter:5d} tokens {tokens:5d} {name} N {N:5d} K {K:5d} touched {touched:3d} | 128: {n1:9.1f} {n2:9.1f} | "
+                     f"64: {o1:9.1f} {o2:9.1f} | 64 / 128 {min(o1, o2) / min(n1, n2):5.2f} | {flop / tn / 1e12:7.1f} TFLOP/s, "
+                     f"{max(t_f, t_b) / tn:.3f} of the {'mfma' if t_f >= t_b else 'hbm'} bound")
+                del aq, As, c
+
+            def full(min_slots):   # the threshold of _block_size_m: 0 -> always 128, out of reach -> 16 / 64
+                def run():
+                    fm.TILE_MIN_SLOTS = min_slots
+                    return fused_experts(x, w1, w2, topk_w, ids, use_fp8_w8a8=True, w1_scale=w1_s, w2_scale=w2_s,
+                                         block_shape=[128, 128])
+                return run
+            keep = fm.TILE_MIN_SLOTS
+            try:
+                n1, n2, o1, o2 = time_pair(full(0), full(1 << 30), a.iters)
+            finally:
+                fm.TILE_MIN_SLOTS = keep
+            rule = 16 if slots <= 16 * E else 64     # what _block_size_m picks without the tile kernel
+            emit(f"  I {inter:5d} tokens {tokens:5d} fused_experts | 128: {n1:9.1f} {n2:9.1f} | {rule}: {o1:9.1f} {o2:9.1f} | "
+                 f"{rule} / 128 {min(o1, o2) / min(n1, n2):5.2f}")
         del w1, w2
         torch.cuda.empty_cache()
     return 0
@@ -143,7 +210,7 @@ def mxfp4_mode(a, dev, emit, fp8_rand, time_pair):
             touched, slots = ids.unique().numel(), tokens * TOPK
             x = torch.randn((tokens, H), device=dev, dtype=torch.bfloat16) / 10
             tw = topk_w.reshape(-1).contiguous()
-            bm = _block_size_m(tokens, TOPK, E)
+            bm = min(_block_size_m(tokens, TOPK, E), 64)
             al = moe_align_block_size(ids, bm, E)
             for name, top_k, a_rows in (("w1", TOPK, tokens), ("w2", 1, slots)):
                 N, K = f8[name].shape[1], f8[name].shape[2]

@@ -299,7 +299,8 @@ def moe_block_fp8_gemm(c: torch.Tensor, a: torch.Tensor, b: torch.Tensor, a_scal
                        num_tokens_post_padded: torch.Tensor, mul_routed_weight: bool, top_k: int,
                        block_size_m: int) -> None:
     """c[t] = (topk_weights[t] *) a[t // top_k] @ b[expert of t].T with 1 x 128 / 128 x 128 block
-    scales, for the flat (token, k) slots t that ``sorted_token_ids`` lists."""
+    scales, for the flat (token, k) slots t that ``sorted_token_ids`` lists; ``block_size_m`` 16 or 64 (the
+    weight-streaming kernel) or 128 (the tile kernel)."""
     torch.ops._C.moe_block_fp8_gemm(c, a, b, a_scales, b_scales, topk_weights, sorted_token_ids,
                                     expert_ids, num_tokens_post_padded, mul_routed_weight, top_k,
                                     block_size_m)

@@ -34,6 +34,34 @@
 //     Launch order: blockIdx.x = m_block * strip_groups + strip_group, so the workgroups of an expert
 //     are adjacent, and the next m-block of a busy expert follows its first while the weights are in L2.
 //
+// (a') Grouped tile kernel, block_size_m = 128 (prefill: an expert sees a hundred rows or more, and
+//     the streaming form would read its weights again for every 64 of them).  The same contract; the
+//     data movement of scaled_mm_block_tile_kernel<out_t, 128> (scaled_mm_block.hip) over a gathered A
+//     operand.  A workgroup of 4 waves owns 128 sorted rows of ONE expert x 128 output columns = one
+//     weight-scale column, so Bs[e, n0 / 128, kb] is a scalar load; every wave a 64 x 64 sub-tile =
+//     4 x 4 MFMA tiles, zero C operand, folded with fma(partial, As * Bs, acc) into ONE sequential fp32
+//     accumulator (the streaming form adds KS partial sums: results differ in the last bits).
+//     Staging is global_load_lds, 16 B per lane, into the XOR-swizzled [rows][128 B] image, a ring of 4
+//     stages, one barrier per K block.  The source address of an LDS-DMA is per lane, so the gather
+//     is free: a staging lane reads its rows' slots from sorted_token_ids once, before the loop,
+//     clamps them, and keeps a + (slot / top_k) * lda; the weight rows come from b + e * b_stride_e.
+//     The 128 activation scales of a K block travel with the stage (one 4-byte LDS-DMA per lane,
+//     gathered by the same row index through as_stride_m / as_stride_k), so the loop's only
+//     vector-memory instructions are the 9 LDS-DMAs per stage that every wave issues, and the one
+//     hand-counted s_waitcnt vmcnt((4 - 2) * 9) in front of the barrier is provable (checked in the
+//     ISA: the slot loads are all waited for in front of the first LDS-DMA).
+//     Epilogue: routed weight of the row in fp32, one rounding, the 128 x 128 image in LDS over the
+//     stages, then whole rows scattered to C row t in 16-byte pieces (scalar where c, ldc or a ragged
+//     N do not allow); padding rows are skipped, an absent expert stores zeros through the same loop.
+//     Grid: ceil(max_num_tokens_padded / 128) x ceil(N / 128) workgroups, a host-side bound.  The
+//     USED count comes from *num_tokens_post_padded; workgroups past it exit before any barrier, the
+//     others are renumbered so that each of the 8 XCDs (hardware workgroup i runs on XCD i % 8) gets
+//     one contiguous run of (m-block, n-tile) pairs, n-tile fastest: the n-tiles of an m-block share
+//     its gathered rows in that XCD's L2, and the next m-block of a busy expert follows while its
+//     weight panels may still be there.  The run is cut from the used count: cut from the grid, the
+//     last XCDs would hold nothing but exiting workgroups.  Effect on L2 hits: not measured.
+//     The MFMAs of 16-row tiles that hold only padding are NOT skipped (not built, not measured).
+//
 // (b) moe_align_block_size: one workgroup of 1024 threads; LDS histogram over the experts, block-wide
 //     exclusive scan of the padded counts, expert_ids by binary search over the segment starts, then
 //     the scatter through LDS cursors.  Ids outside [0, E) are skipped (the reference would index out
@@ -52,6 +80,7 @@
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage, bf16 out):
 //   gemm MT 1, KS 8 / 2: 104 / 104 VGPRs, 0 AGPRs, scratch 0, LDS  8768 B, occupancy 4 waves / SIMD
 //   gemm MT 4, KS 8 / 2: 150 / 148 VGPRs, 0 AGPRs, scratch 0, LDS 35072 B, occupancy 3 waves / SIMD
+//   gemm tile 128: 166 VGPRs + 20 AGPRs, scratch 0, LDS 133632 B, 1 workgroup (4 waves) / CU = 1 wave / SIMD
 //   align: 26 VGPRs, LDS 8260 B;  silu_and_mul_group_quant: 45 VGPRs, no LDS;  moe_sum: 30 VGPRs, no LDS;
 //   all scratch 0, occupancy 8
 // Nothing is allocated or synchronised and there is no workspace: every entry point is graph-capturable.
@@ -195,6 +224,258 @@ __global__ __launch_bounds__(MOE_WAVES * 64) void moe_block_gemm_kernel(
     if (topk_w) v *= topk_w[t];
     c[(int64_t)t * ldc + n] = from_f32<out_t>(v);
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// (a') grouped tile kernel, block_size_m 128
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int moe_qswz(int row) {
+  return ((row >> 1) & 1) | (((row >> 2) & 1) << 2);
+}
+// LDS reads of the K loop as inline asm: a C++ LDS load is ordered by hipcc behind ALL outstanding
+// LDS-DMA (s_waitcnt vmcnt(0)), which would serialise the ring with the math
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+template <int OFF>
+__device__ __forceinline__ i32x4 moe_lds_read16(uint32_t addr) {
+  i32x4 v;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+  return v;
+}
+template <int OFF>
+__device__ __forceinline__ float moe_lds_read4(uint32_t addr) {
+  float v;
+  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+  return v;
+}
+
+constexpr int MOE_TILE_BM = 128;
+
+template <typename out_t>
+__global__ __launch_bounds__(MOE_TILE_BM * 2) void moe_block_gemm_tile_kernel(
+    out_t* __restrict__ c, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+    const float* __restrict__ a_scales, const float* __restrict__ b_scales, const int* __restrict__ sorted_ids,
+    const int* __restrict__ expert_ids, const int* __restrict__ num_post, const float* __restrict__ topk_w, int nvt,
+    int top_k, int E, int N, int K, int max_padded, int tiles_n, int64_t lda, int64_t b_se, int64_t b_sn, int64_t ldc,
+    int64_t as_sm, int64_t as_sk, int64_t bs_se, int64_t bs_sn, int64_t bs_sk, int vec_store) {
+  constexpr int BM = MOE_TILE_BM, QB = MOE_QB;
+  constexpr int NW = BM / 32;                        // 4 waves: 2 x 2, each 64 x 64
+  constexpr int A_BYTES = BM * QB, W_BYTES = QB * QB, STAGE = A_BYTES + W_BYTES;
+  constexpr int RPR = 8 * NW;                        // rows staged per glds round
+  constexpr int A_ROUNDS = BM / RPR, W_ROUNDS = QB / RPR;
+  constexpr int OROW = QB + 8;                       // output image: row stride in elements (272 B)
+  constexpr int NST = 4;                             // ring stages: NST - 1 K blocks in flight
+  constexpr int STRIP = BM * 4;                      // the BM activation scales of a K block
+  constexpr int PER = A_ROUNDS + W_ROUNDS + 1;       // LDS-DMA instructions per lane and stage
+  static_assert(BM * OROW * (int)sizeof(out_t) <= NST * STAGE, "the output image overlays the stages");
+  static_assert(NST * (STAGE + STRIP) + BM * 4 <= 160 * 1024 && (NST - 2) * PER <= 63, "LDS size, vmcnt is 6 bits");
+  __shared__ __attribute__((aligned(16))) uint8_t lds[NST * (STAGE + STRIP)];
+  __shared__ int stok[BM];
+
+  // The grid is the host-side bound; the blocks in use are counted here.  Hardware workgroup i runs on
+  // XCD i % 8: give every XCD a contiguous run of the USED (m-block, n-tile) pairs, n fastest, so that
+  // the n-tiles of an m-block (which share its 128 gathered rows) and the next m-block of the same
+  // expert (which shares its weight panels) meet in one L2.  The run is cut from the used count, not
+  // from the grid, or the last XCDs would hold only blocks that exit.
+  const int padded = min(*num_post, max_padded);     // never past the caller's buffers
+  const int used = (padded + BM - 1) / BM * tiles_n;
+  int wg = blockIdx.x;
+  if (wg >= used) return;                            // workgroup-uniform, before any barrier
+  {
+    const int q = used / 8, r = used % 8, xcd = wg % 8, idx = wg / 8;
+    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  const int mb = wg / tiles_n, tn = wg - mb * tiles_n;
+  const int m0 = mb * BM, n0 = tn * QB;
+  const int e = __builtin_amdgcn_readfirstlane(expert_ids[mb]);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c16 = lane & 15, g4 = lane >> 4;
+  const int wm = wave >> 1, wn = wave & 1;
+
+  // flat slot of a sorted row, nvt or more = padding
+  auto slot_of = [&](int row) { return m0 + row < padded ? sorted_ids[m0 + row] : nvt; };
+  if (tid < BM) {
+    const int t = slot_of(tid);
+    stok[tid] = (unsigned)t < (unsigned)nvt ? t : -1;   // -1: never stored
+  }
+
+  // whole rows out of the image in LDS (or zeros): thread -> 16-byte piece tid & 15 of rows tid >> 4, + 16, ...
+  out_t* ot = reinterpret_cast<out_t*>(lds);
+  auto store_rows = [&](bool zero) {
+    const int chunk = tid & 15;
+    const int n = n0 + chunk * 8;
+    if (n >= N) return;
+    for (int row = tid >> 4; row < BM; row += NW * 4) {
+      const int t = stok[row];
+      if (t < 0) continue;
+      uint4 v = {0u, 0u, 0u, 0u};                    // sixteen zero bytes are eight zeros of either type
+      if (!zero) v = *reinterpret_cast<const uint4*>(ot + row * OROW + chunk * 8);
+      out_t* op = c + (int64_t)t * ldc + n;
+      if (vec_store && n + 8 <= N) {
+        *reinterpret_cast<uint4*>(op) = v;
+      } else {
+        const out_t* ev = reinterpret_cast<const out_t*>(&v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (n + j < N) op[j] = ev[j];
+      }
+    }
+  };
+
+  if ((unsigned)e >= (unsigned)E) {
+    // an expert of another rank (expert_map): zeros for the valid rows
+    __syncthreads();
+    store_rows(true);
+    return;
+  }
+
+  // staging: in round r wave w fills rows [RPR r + 8 w, +8); lane -> (row = lane >> 3, slot = lane & 7)
+  // loads logical chunk slot ^ f(row), so the lane-linear LDS image is the swizzled tile.  The A source
+  // is per lane, so the gather costs nothing: the lane reads its row's slot once, here.  Padding
+  // entries and weight rows past N re-read a valid row: their outputs are never stored.
+  const int srow = lane >> 3, sslot = lane & 7;
+  const uint8_t* a_src[A_ROUNDS];
+  const uint8_t* w_src[W_ROUNDS];
+#pragma unroll
+  for (int r = 0; r < A_ROUNDS; ++r) {
+    const int row = RPR * r + 8 * wave + srow;
+    const int m = (int)min((unsigned)slot_of(row), (unsigned)(nvt - 1)) / top_k;
+    a_src[r] = a + (int64_t)m * lda + ((sslot ^ moe_qswz(row)) << 4);
+  }
+#pragma unroll
+  for (int r = 0; r < W_ROUNDS; ++r) {
+    const int row = RPR * r + 8 * wave + srow;
+    const int n = min(n0 + row, N - 1);
+    w_src[r] = b + (int64_t)e * b_se + (int64_t)n * b_sn + ((sslot ^ moe_qswz(row)) << 4);
+  }
+  // the activation scales of a K block travel with its tile: every wave gathers 64 of the 128 values
+  // As[row of slot, kb] into the stage's strip with one 4-byte LDS-DMA (waves 2 and 3 repeat the rows
+  // of waves 0 and 1: the same values to the same place, so every wave counts PER loads)
+  const int strip_row = (wave & 1) * 64;
+  const float* as_src =
+      a_scales + (int64_t)((int)min((unsigned)slot_of(strip_row + lane), (unsigned)(nvt - 1)) / top_k) * as_sm;
+  auto stage_load = [&](int stage, int kb) {
+    uint8_t* base = lds + stage * STAGE + 8 * wave * QB;
+    const int64_t k0 = (int64_t)kb * QB;
+#pragma unroll
+    for (int r = 0; r < A_ROUNDS; ++r)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[r] + k0),
+                                       (__attribute__((address_space(3))) void*)(base + RPR * r * QB), 16, 0, 0);
+#pragma unroll
+    for (int r = 0; r < W_ROUNDS; ++r)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w_src[r] + k0),
+                                       (__attribute__((address_space(3))) void*)(base + A_BYTES + RPR * r * QB), 16, 0,
+                                       0);
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) void*)(as_src + (int64_t)kb * as_sk),
+        (__attribute__((address_space(3))) void*)(lds + NST * STAGE + stage * STRIP + strip_row * 4), 4, 0, 0);
+  };
+  const float* bs_ptr = b_scales + (int64_t)e * bs_se + (int64_t)tn * bs_sn;   // workgroup-uniform
+
+  f32x4 acc[4][4];   // [nt][mt]
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  // fragment read addresses: the swizzle depends on c16 only, so tile t is an immediate offset
+  // t * 16 * 128 from one per-lane base per 16-byte half (j) and operand; likewise the lane's four
+  // activation scales (row c16 of each of its m-tiles) in the strip
+  const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
+  uint32_t w_addr[2], a_addr[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int ch = ((2 * g4 + j) ^ moe_qswz(c16)) << 4;
+    w_addr[j] = lds_base + A_BYTES + (wn * 64 + c16) * QB + ch;
+    a_addr[j] = lds_base + (wm * 64 + c16) * QB + ch;
+  }
+  const uint32_t s_addr = lds_base + NST * STAGE + (wm * 64 + c16) * 4;
+
+  // Ring of NST stages, NST - 1 K blocks in flight.  Per block: wait for the own LDS-DMA of block kb
+  // (everything but the NST - 2 younger stages; near the end fewer are in flight, so drain) ->
+  // s_barrier (everybody's has landed, and everybody is past its reads of the stage refilled next) ->
+  // request all fragments and the four scales of the block -> issue the DMA of block kb + NST - 1 ->
+  // lgkmcnt(0) -> 16 MFMAs with a zero C operand, each folded into the accumulators by 4 FMAs.
+  // The slot reads above are ordinary vector loads: they stay in front of the first LDS-DMA, so that
+  // the wait below counts LDS-DMAs only.
+  const int nk = K / QB;
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int s = 0; s < NST - 1; ++s)
+    if (s < nk) stage_load(s, s);
+  int cur = 0, nxt = NST - 1;   // stage of block kb / of block kb + NST - 1
+  for (int kb = 0; kb < nk; ++kb) {
+    if (kb + NST - 1 <= nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * PER) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+
+    const uint32_t so = cur * STAGE;
+    const uint32_t wa0 = w_addr[0] + so, wa1 = w_addr[1] + so, aa0 = a_addr[0] + so, aa1 = a_addr[1] + so;
+    const uint32_t sa = s_addr + cur * STRIP;
+    i32x4 wl[4], wh[4], al[4], ah[4];
+    float as[4];
+    static_for<4>([&](auto tc) {
+      constexpr int t = decltype(tc)::value;
+      wl[t] = moe_lds_read16<t * 16 * QB>(wa0);
+      wh[t] = moe_lds_read16<t * 16 * QB>(wa1);
+      al[t] = moe_lds_read16<t * 16 * QB>(aa0);
+      ah[t] = moe_lds_read16<t * 16 * QB>(aa1);
+      as[t] = moe_lds_read4<t * 64>(sa);
+    });
+    if (kb + NST - 1 < nk) stage_load(nxt, kb + NST - 1);
+    cur = cur + 1 == NST ? 0 : cur + 1;
+    nxt = nxt + 1 == NST ? 0 : nxt + 1;
+    const float bs = bs_ptr[(int64_t)kb * bs_sk];
+    // the fragments pass through the wait as in/out operands, so their consumers stay behind it
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(wl[0]), "+v"(wl[1]), "+v"(wl[2]), "+v"(wl[3]), "+v"(wh[0]), "+v"(wh[1]), "+v"(wh[2]),
+                   "+v"(wh[3]), "+v"(al[0]), "+v"(al[1]), "+v"(al[2]), "+v"(al[3]), "+v"(ah[0]), "+v"(ah[1]),
+                   "+v"(ah[2]), "+v"(ah[3]), "+v"(as[0]), "+v"(as[1]), "+v"(as[2]), "+v"(as[3]));
+    __builtin_amdgcn_sched_barrier(0);
+
+    i32x8 wf[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) wf[t] = __builtin_shufflevector(wl[t], wh[t], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const float s = as[mt] * bs;
+      const i32x8 af = __builtin_shufflevector(al[mt], ah[mt], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        const f32x4 p = moe_block_mfma(wf[nt], af);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[nt][mt][r] = fmaf(p[r], s, acc[nt][mt][r]);
+      }
+    }
+  }
+
+  // ---- epilogue: lane holds C^T[n = 16 nt + 4 g4 + r][m = 16 mt + c16]; routed weight of the row in
+  // fp32, one rounding, through LDS (overlaying the stages), whole rows out to C row stok[row]
+  __syncthreads();   // everybody is past its fragment reads
+  float rw[4] = {1.f, 1.f, 1.f, 1.f};
+  if (topk_w) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const int t = stok[wm * 64 + mt * 16 + c16];
+      if (t >= 0) rw[mt] = topk_w[t];
+    }
+  }
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+    const int nl = wn * 64 + nt * 16 + 4 * g4;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const int ml = wm * 64 + mt * 16 + c16;
+      struct alignas(8) V4 { out_t e[4]; } pk;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pk.e[r] = from_f32<out_t>(acc[nt][mt][r] * rw[mt]);   // x 1.0f is exact
+      *reinterpret_cast<V4*>(ot + ml * OROW + nl) = pk;
+    }
+  }
+  __syncthreads();
+  store_rows(false);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -362,6 +643,16 @@ static void launch_moe_gemm(void* c, const void* a, const void* b, const float* 
   // instead of 7, and a workgroup writes 64-column rows); KS 8 is kept for narrow outputs with a long
   // K, where four strips per workgroup leave too few workgroups for 256 CUs.  The N threshold lies
   // between the measured 512 and 4096: 1024 is NOT measured.
+  if (bm == MOE_TILE_BM) {
+    // (a'): one workgroup per (m-block, 128-column tile) of the host-side bound
+    const int tiles_n = ceil_div(N, MOE_QB);
+    const int vec = (ldc % 8 == 0 && ((((uintptr_t)c) & 15) == 0)) ? 1 : 0;
+    hipLaunchKernelGGL((moe_block_gemm_tile_kernel<T>), dim3((unsigned)(ceil_div(max_padded, bm) * tiles_n)),
+                       dim3(MOE_TILE_BM * 2), 0, st, (T*)c, (const uint8_t*)a, (const uint8_t*)b, as, bs, sorted_ids,
+                       expert_ids, num_post, topk_w, nvt, top_k, E, N, K, max_padded, tiles_n, lda, b_se, b_sn, ldc,
+                       as_sm, as_sk, bs_se, bs_sn, bs_sk, vec);
+    return;
+  }
   const int nkb = K / MOE_QB;
   const int ks = g_moe_ks == 8 || g_moe_ks == 2 ? g_moe_ks : (nkb >= 16 && N <= 1024 ? 8 : 2);
   const int nsg = ceil_div(N, 16 * (MOE_WAVES / ks));
@@ -387,8 +678,8 @@ extern "C" int vllm_amd_moe_blockwise_gemm(void* c, const void* a, const void* b
                                            int64_t bs_stride_n, int64_t bs_stride_k, int out_dtype, void* stream) {
   const char* op = "moe_blockwise_gemm";
   VA_REQUIRE(num_valid_tokens >= 0 && N >= 0 && K >= 0 && num_experts >= 0, VLLM_AMD_EINVAL, "%s: negative dimension", op);
-  VA_REQUIRE(block_size_m == 16 || block_size_m == 64, VLLM_AMD_EUNSUPPORTED,
-             "%s: block_size_m = %d must be 16 or 64", op, block_size_m);
+  VA_REQUIRE(block_size_m == 16 || block_size_m == 64 || block_size_m == MOE_TILE_BM, VLLM_AMD_EUNSUPPORTED,
+             "%s: block_size_m = %d must be 16 or 64 (streaming) or 128 (tile)", op, block_size_m);
   VA_REQUIRE(out_dtype == VLLM_AMD_BF16 || out_dtype == VLLM_AMD_F16, VLLM_AMD_EUNSUPPORTED,
              "%s: out dtype must be bfloat16 or float16", op);
   VA_REQUIRE(K > 0 && K % MOE_QB == 0, VLLM_AMD_EUNSUPPORTED,

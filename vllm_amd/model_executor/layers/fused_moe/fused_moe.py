@@ -36,6 +36,8 @@ from .moe_align_block_size import moe_align_block_size
 
 #: tokens per pass (VLLM_FUSED_MOE_CHUNK_SIZE's default in the reference, fused_moe.py:1402)
 CHUNK_SIZE = 32768
+#: average slots per expert from which the fp8 grouped GEMM runs its 128-row tile kernel
+TILE_MIN_SLOTS = 64
 
 
 def _block_size_m(num_tokens: int, top_k: int, num_experts: int) -> int:
@@ -44,7 +46,17 @@ def _block_size_m(num_tokens: int, top_k: int, num_experts: int) -> int:
     # Measured at E 256, top-k 8 (tools/bench_moe.py, profiles/moe_block_fp8.txt): 16 is 1.5 - 2.2 x
     # faster than 64 from 1 to 256 tokens, 64 is 1.06 - 1.32 x faster at 4096 tokens; the crossover
     # itself (between 256 and 4096 tokens) is not measured, the rule puts it at 512.
-    return 16 if num_tokens * top_k <= 16 * num_experts else 64
+    # 128 (the grouped tile kernel: LDS-staged 128 x 128 tiles, the weights read once per 128 rows) from
+    # TILE_MIN_SLOTS slots per expert on.  Measured at E 256, top-k 8 (tools/bench_moe.py --tile,
+    # profiles/moe_block_fp8_tile.txt), the whole fused_experts call with 128 against this rule without it:
+    # 0.86 - 0.89 x at 256 tokens, 1.16 - 1.30 x at 512, 1.9 - 2.1 x at 1024, 2.6 - 3.3 x at 2048, 2.9 - 3.8 x
+    # at 4096, 3.4 - 4.6 x at 16384.  128 wins from 512 tokens = 16 slots per expert on; the threshold stays
+    # at 64 (2048 tokens there), the lowest value this rule allows itself: every batch below it keeps the
+    # kernel, and the bits, it had.
+    slots = num_tokens * top_k
+    if slots >= TILE_MIN_SLOTS * num_experts:
+        return 128
+    return 16 if slots <= 16 * num_experts else 64
 
 
 def _gating_2d(name: str, hidden_states: torch.Tensor, gating_output: torch.Tensor) -> None:
@@ -105,7 +117,8 @@ def invoke_fused_moe_kernel(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor,
                             block_shape: Optional[list[int]] = None) -> None:
     """The grouped GEMM: C[t] = (topk_weights[t] *) A[t // top_k] @ B[expert of slot t].T for the
     slots ``sorted_token_ids`` lists; ``config["BLOCK_SIZE_M"]`` is the block size the ids were
-    aligned to (16 or 64).  ``compute_type`` is implied by C's dtype."""
+    aligned to (16 or 64: the weight-streaming kernel; 128: the tile kernel).  ``compute_type`` is implied by
+    C's dtype."""
     for name, flag in (("use_int8_w8a8", use_int8_w8a8), ("use_int8_w8a16", use_int8_w8a16),
                        ("use_int4_w4a16", use_int4_w4a16), ("per_channel_quant", per_channel_quant)):
         if flag:
@@ -212,6 +225,7 @@ def fused_experts(hidden_states: torch.Tensor, w1: torch.Tensor, w2: torch.Tenso
         cache3 = torch.zeros((m, top_k, K), device=dev, dtype=dtype)
         bm = config["BLOCK_SIZE_M"]
         if use_mxfp4_w4a4:
+            bm = min(bm, 64)                                  # the MXFP4 GEMM has no tile form
             q1 = torch.empty((m, K // 2), device=dev, dtype=torch.uint8)
             s1 = torch.empty((m, K // 32), device=dev, dtype=torch.uint8)
             q2 = torch.empty((m * top_k, N // 4), device=dev, dtype=torch.uint8)
