@@ -216,6 +216,54 @@ int vllm_amd_mla_decode_fp8(
     int64_t cache_entry_stride, int64_t block_table_stride, int dtype, int cache_dtype,
     int kv_dtype, int index_bits, const float* kv_scale, void* stream);
 
+/* MLA prefill: ragged (varlen) flash attention forward with a q.k width of 192 and a v width of 128; replaces
+ * torch.cat + the padded v + flash_attn_varlen_func of MLACommonImpl._forward_prefill /
+ * _compute_prefill_context (vllm/v1/attention/backends/mla/common.py:821-857, 1017-1127).
+ * q [num_q_tokens, num_heads, 192], out [num_q_tokens, num_heads, 128], float16 / bfloat16, last dimension
+ * contiguous.  K comes in split form and is never copied: k_nope [Tk, num_heads, 128] and v [Tk, num_heads, 128]
+ * are strided views (typically the two halves of kv_b_proj's [Tk, num_heads, 256] output), k_pe [Tk, *, 64] has
+ * its own strides; kp_stride_h == 0 is one rope key shared by all heads, and a concatenated k [Tk, H, 192] is
+ * k_nope = k, k_pe = k + 128 with head stride 192.  Strides are multiples of 8 elements, pointers 16-byte aligned.
+ * cu_seqlens_q / cu_seqlens_k: int32 [batch + 1]; max_seqlen_q must bound every query length (it sizes the grid).
+ * causal != 0: bottom-right aligned, query i of Sq sees keys j <= i + Sk - Sq.  lse: NULL or float
+ * [num_heads, lse_stride_h >= num_q_tokens], ln(sum_j exp(sm_scale q.k_j)).  A row without a visible key gets
+ * out = 0 and lse = -inf.  batch == 0 or num_q_tokens == 0: nothing is launched. */
+int vllm_amd_mla_prefill_attention(
+    void* out, float* lse, const void* q, const void* k_nope, const void* k_pe, const void* v,
+    const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int batch, int64_t num_q_tokens,
+    int num_heads, int qk_head_dim, int v_head_dim, int pe_dim, int max_seqlen_q, float sm_scale,
+    int causal, int64_t q_stride_t, int64_t q_stride_h, int64_t o_stride_t, int64_t o_stride_h,
+    int64_t kn_stride_t, int64_t kn_stride_h, int64_t kp_stride_t, int64_t kp_stride_h,
+    int64_t v_stride_t, int64_t v_stride_h, int64_t lse_stride_h, int dtype, void* stream);
+
+/* Replaces merge_attn_states (vllm/attention/ops/triton_merge_attn_states.py:12-97, a Triton kernel):
+ * out = prefix_out * e^(prefix_lse - m) / s + suffix_out * e^(suffix_lse - m) / s, out_lse (may be NULL) =
+ * log(s) + m.  Outputs [num_tokens, num_heads, head_size] float16 / bfloat16 (16-byte aligned, strides multiples
+ * of 8 elements), head_size a multiple of 8 up to 512; the three lse are float [num_heads, lse_stride_h]; an lse
+ * of +inf reads as -inf.  Unlike the reference, a row whose two lse are both -inf gets out = 0 and
+ * out_lse = -inf (not NaN). */
+int vllm_amd_merge_attn_states(
+    void* out, float* out_lse, const void* prefix_out, const float* prefix_lse,
+    const void* suffix_out, const float* suffix_lse, int64_t num_tokens, int num_heads,
+    int head_size, int64_t out_stride_t, int64_t out_stride_h, int64_t prefix_stride_t,
+    int64_t prefix_stride_h, int64_t suffix_stride_t, int64_t suffix_stride_h,
+    int64_t lse_stride_h, int dtype, void* stream);
+
+/* Replaces torch.ops._C_cache_ops.gather_cache (schema csrc/torch_bindings.cpp:710-714,
+ * csrc/cache_kernels.cu:578-734, python vllm/_custom_ops.py:1684-1691):
+ * dst[cu_seq_lens[b] + i, :entry_size] = src_cache[block_table[b, seq_starts[b] / block_size + i / block_size],
+ * i % block_size, :] for i < cu_seq_lens[b + 1] - cu_seq_lens[b]; seq_starts may be NULL; rows of dst past
+ * cu_seq_lens[batch_size] (and past dst_rows, the rows dst has) are not written.  kv_dtype AUTO: a copy of
+ * elements of elem_size (1, 2 or 4) bytes.  FP8_E4M3 (beyond the reference): src_cache holds e4m3fn bytes and
+ * dst, of `dtype` float16 / bfloat16, gets float(byte) * *scale (device float[1]); entry size and strides must
+ * then be multiples of 8 elements. */
+int vllm_amd_gather_cache(
+    const void* src_cache, void* dst, const int32_t* block_table, const int32_t* cu_seq_lens,
+    const int32_t* seq_starts, int batch_size, int64_t dst_rows, int block_size, int entry_size,
+    int64_t block_table_stride, int64_t cache_block_stride, int64_t cache_entry_stride,
+    int64_t dst_entry_stride, int elem_size, int dtype, int kv_dtype, const float* scale,
+    void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* fp8 (e4m3fn) quantisation, input [num_tokens, hidden] contiguous           */
 /* ------------------------------------------------------------------------- */

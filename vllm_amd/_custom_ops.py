@@ -149,6 +149,34 @@ def convert_fp8(output: torch.Tensor, input: torch.Tensor, scale: float = 1.0,
     torch.ops._C_cache_ops.convert_fp8(output, input, scale, kv_dtype)
 
 
+# vllm/_custom_ops.py:1684-1691.  Beyond the reference: with the keyword `scale` (float32, one element, on the
+# cache's device) src_cache is the fp8 (e4m3fn) latent cache and dst, float16 / bfloat16, gets float(byte) * scale --
+# the value the fp8 MLA decode reads.  That form goes through the C ABI; the torch op keeps the same-dtype contract.
+def gather_cache(src_cache: torch.Tensor, dst: torch.Tensor, block_table: torch.Tensor,
+                 cu_seq_lens: torch.Tensor, batch_size: int,
+                 seq_starts: Optional[torch.Tensor] = None, *, scale: Optional[torch.Tensor] = None) -> None:
+    if scale is None:
+        torch.ops._C_cache_ops.gather_cache(src_cache, dst, block_table, cu_seq_lens, batch_size, seq_starts)
+        return
+    from ._lib import KV_FP8_E4M3, check, lib
+    from ._torch_ops import _dev, _dt, _ptr, _stream
+    if (src_cache.dtype not in (torch.uint8, torch.float8_e4m3fn) or src_cache.dim() != 3 or dst.dim() != 2
+            or src_cache.stride(2) != 1 or dst.stride(1) != 1 or dst.shape[1] != src_cache.shape[2]
+            or block_table.dtype != torch.int32 or cu_seq_lens.dtype != torch.int32 or block_table.stride(1) != 1
+            or not cu_seq_lens.is_contiguous() or cu_seq_lens.numel() <= batch_size
+            or (seq_starts is not None and (seq_starts.dtype != torch.int32 or not seq_starts.is_contiguous()))
+            or scale.dtype != torch.float32 or scale.numel() != 1
+            or any(t.device != src_cache.device for t in (dst, block_table, cu_seq_lens, scale))):
+        raise RuntimeError("gather_cache with scale: src_cache [NUM_BLOCKS, BLOCK_SIZE, ENTRY] uint8 / float8_e4m3fn, dst "
+                           "[TOT_TOKENS, ENTRY] float16 / bfloat16, int32 block_table / cu_seq_lens / seq_starts and a "
+                           "float32 scale of one element, all on one device, are required")
+    with _dev(src_cache):
+        check(lib.vllm_amd_gather_cache(
+            _ptr(src_cache), _ptr(dst), _ptr(block_table), _ptr(cu_seq_lens), _ptr(seq_starts), batch_size,
+            dst.shape[0], src_cache.shape[1], src_cache.shape[2], block_table.stride(0), src_cache.stride(0),
+            src_cache.stride(1), dst.stride(0), 2, _dt(dst), KV_FP8_E4M3, _ptr(scale), _stream(src_cache)))
+
+
 # vllm/_custom_ops.py:1244-1304
 def scaled_fp8_quant(
     input: torch.Tensor,

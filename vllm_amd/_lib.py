@@ -47,6 +47,13 @@ SIGNATURES = {
     "vllm_amd_mla_decode_fp8": [
         _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _f, _i64, _i64, _i64, _i64, _i64,
         _i64, _i64, _i, _i, _i, _i, _vp, _vp],
+    "vllm_amd_mla_prefill_attention": [
+        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _f, _i, _i64, _i64, _i64, _i64,
+        _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp],
+    "vllm_amd_merge_attn_states": [
+        _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp],
+    "vllm_amd_gather_cache": [
+        _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i64, _i64, _i64, _i64, _i, _i, _i, _vp, _vp],
     "vllm_amd_static_scaled_fp8_quant": [_vp, _vp, _vp, _i64, _i, _i, _vp],
     "vllm_amd_dynamic_scaled_fp8_quant": [_vp, _vp, _vp, _i64, _i, _i, _vp],
     "vllm_amd_dynamic_per_token_scaled_fp8_quant": [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp],

@@ -99,6 +99,7 @@ reshape_and_cache = torch.ops._C_cache_ops.reshape_and_cache
 reshape_and_cache_flash = torch.ops._C_cache_ops.reshape_and_cache_flash
 concat_and_cache_mla = torch.ops._C_cache_ops.concat_and_cache_mla
 convert_fp8 = torch.ops._C_cache_ops.convert_fp8
+gather_cache = torch.ops._C_cache_ops.gather_cache
 copy_blocks = torch.ops._C_cache_ops.copy_blocks
 swap_blocks = torch.ops._C_cache_ops.swap_blocks
 static_scaled_fp8_quant = torch.ops._C.static_scaled_fp8_quant
@@ -135,6 +136,7 @@ def _no_output(*args, **kwargs) -> None:
 
 for _name in ("mxfp4_quant", "silu_and_mul_mxfp4_quant", "moe_mxfp4_gemm"):
     torch.library.register_fake(f"_C::{_name}")(_no_output)
+torch.library.register_fake("_C_cache_ops::gather_cache")(_no_output)
 #: device-side BlockTable.compute_slot_mapping (vllm/v1/worker/block_table.py:84-99); not a
 #: reference op -- the reference does this with numpy on the host
 compute_slot_mapping = torch.ops._vllm_amd_C.compute_slot_mapping

@@ -710,3 +710,124 @@ extern "C" int vllm_amd_concat_and_cache_mla(const void* kv_c, const void* k_pe,
   CM(bf16_t, true);
 #undef CM
 }
+
+// ---------------------------------------------------------------------------
+// gather_cache: dst[cu_seq_lens[b] + i, :] = src_cache[block_table[b, seq_starts[b] / block_size + i / block_size],
+// i % block_size, :] (csrc/cache_kernels.cu:578-734; the remainder of seq_starts[b] / block_size is dropped, :619-621).
+// The work is split by DESTINATION rows: a workgroup takes 16 rows wherever they fall, so one long sequence is spread
+// over as many workgroups as its length asks for (the reference gives every sequence 16).  The total is only known
+// on the device: the grid covers the rows dst has, workgroups past cu_seq_lens[batch] leave at once.  The first 16
+// threads find their row's sequence (binary search in cu_seq_lens) and source offset, then every thread moves
+// vectors of V bytes (16 where widths, strides and pointers allow).  DEQ: src holds e4m3 bytes, dst gets
+// float(byte) * *scale in its 16-bit type, 8 bytes -> one 16-byte store (the value vllm_amd_mla_decode_fp8 reads).
+// ---------------------------------------------------------------------------
+namespace va {
+constexpr int GC_ROWS = 16;
+
+template <typename V, typename T, bool DEQ>
+__global__ __launch_bounds__(256) void gather_cache_kernel(
+    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const int32_t* __restrict__ block_table,
+    const int32_t* __restrict__ cu_seq_lens, const int32_t* __restrict__ seq_starts, int batch, int64_t dst_rows,
+    int block_size, int vecs_per_row, int64_t bt_stride, int64_t block_bytes, int64_t entry_bytes,
+    int64_t dst_row_bytes, const float* __restrict__ scale_p) {
+  __shared__ int64_t src_off[GC_ROWS];
+  const int64_t row0 = (int64_t)blockIdx.x * GC_ROWS;
+  const int64_t total = min((int64_t)cu_seq_lens[batch], dst_rows);
+  if (row0 >= total) return;
+  if (threadIdx.x < GC_ROWS) {
+    const int64_t r = row0 + threadIdx.x;
+    int64_t o = -1;
+    if (r < total) {
+      int lo = 0, hi = batch;   // the last sequence with cu_seq_lens[b] <= r (empty sequences are passed over)
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (cu_seq_lens[mid] <= r) lo = mid; else hi = mid;
+      }
+      const int i = (int)(r - cu_seq_lens[lo]);
+      const int first = seq_starts != nullptr ? seq_starts[lo] / block_size : 0;
+      const int64_t blk = block_table[lo * bt_stride + first + i / block_size];
+      o = blk * block_bytes + (int64_t)(i % block_size) * entry_bytes;
+    }
+    src_off[threadIdx.x] = o;
+  }
+  __syncthreads();
+  float scale = 1.f;
+  if constexpr (DEQ) scale = *scale_p;
+  for (int it = threadIdx.x; it < GC_ROWS * vecs_per_row; it += 256) {
+    const int rr = it / vecs_per_row, c = it - rr * vecs_per_row;
+    const int64_t so = src_off[rr];
+    if (so < 0) continue;
+    if constexpr (DEQ) {
+      const uint2 w = *reinterpret_cast<const uint2*>(src + so + 8 * c);
+      Vec<T, 8> ov;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f32x2 f = fp8x2_to_f32(j < 2 ? w.x : w.y, j & 1);
+        ov.v[2 * j] = from_f32<T>(f.x * scale);
+        ov.v[2 * j + 1] = from_f32<T>(f.y * scale);
+      }
+      *reinterpret_cast<Vec<T, 8>*>(dst + (row0 + rr) * dst_row_bytes + 16 * c) = ov;
+    } else {
+      *reinterpret_cast<V*>(dst + (row0 + rr) * dst_row_bytes + sizeof(V) * c) =
+          *reinterpret_cast<const V*>(src + so + sizeof(V) * c);
+    }
+  }
+}
+}  // namespace va
+
+/* strides in elements of the tensor they describe; elem_size = bytes of a dst element */
+extern "C" int vllm_amd_gather_cache(const void* src_cache, void* dst, const int32_t* block_table,
+                                     const int32_t* cu_seq_lens, const int32_t* seq_starts, int batch_size,
+                                     int64_t dst_rows, int block_size, int entry_size, int64_t block_table_stride,
+                                     int64_t cache_block_stride, int64_t cache_entry_stride, int64_t dst_entry_stride,
+                                     int elem_size, int dtype, int kv_dtype, const float* scale, void* stream) {
+  VA_REQUIRE(batch_size >= 0 && dst_rows >= 0 && block_size > 0 && entry_size > 0 && block_table_stride >= 0 &&
+                 cache_block_stride >= 0,
+             VLLM_AMD_EINVAL, "gather_cache: bad shape");
+  VA_REQUIRE(kv_dtype == VLLM_AMD_KV_AUTO || kv_dtype == VLLM_AMD_KV_FP8_E4M3, VLLM_AMD_EUNSUPPORTED,
+             "Unsupported data type of kv cache: %d", kv_dtype);
+  const bool deq = kv_dtype == VLLM_AMD_KV_FP8_E4M3;
+  if (deq) {
+    VA_REQUIRE(dtype == VLLM_AMD_F16 || dtype == VLLM_AMD_BF16, VLLM_AMD_EUNSUPPORTED,
+               "gather_cache: an fp8 cache is widened to float16 or bfloat16 only");
+    elem_size = 2;
+  } else {
+    VA_REQUIRE(elem_size == 1 || elem_size == 2 || elem_size == 4, VLLM_AMD_EUNSUPPORTED,
+               "Unsupported data type width: %d", 8 * elem_size);
+  }
+  VA_REQUIRE(cache_entry_stride >= entry_size && dst_entry_stride >= entry_size, VLLM_AMD_EINVAL,
+             "gather_cache: entry strides %lld / %lld < entry size %d", (long long)cache_entry_stride,
+             (long long)dst_entry_stride, entry_size);
+  if (batch_size == 0 || dst_rows == 0) return VLLM_AMD_OK;
+  VA_REQUIRE(src_cache && dst && block_table && cu_seq_lens && (!deq || scale), VLLM_AMD_EINVAL,
+             "gather_cache: null pointer");
+  const int64_t blocks = (dst_rows + GC_ROWS - 1) / GC_ROWS;
+  VA_REQUIRE(blocks < (1ll << 31), VLLM_AMD_EINVAL, "gather_cache: launch too large");
+  const int src_elem = deq ? 1 : elem_size;
+  const int64_t row_bytes = (int64_t)entry_size * src_elem, block_bytes = cache_block_stride * src_elem,
+                entry_bytes = cache_entry_stride * src_elem, dst_row_bytes = dst_entry_stride * elem_size;
+  hipStream_t st = (hipStream_t)stream;
+#define GC(V, T, D, W)                                                                                               \
+  hipLaunchKernelGGL((gather_cache_kernel<V, T, D>), dim3((unsigned)blocks), dim3(256), 0, st,                       \
+                     (const uint8_t*)src_cache, (uint8_t*)dst, block_table, cu_seq_lens, seq_starts, batch_size,     \
+                     dst_rows, block_size, (int)(row_bytes / (W)), block_table_stride, block_bytes, entry_bytes,     \
+                     dst_row_bytes, scale)
+  if (deq) {
+    VA_REQUIRE(entry_size % 8 == 0 && block_bytes % 8 == 0 && entry_bytes % 8 == 0 && dst_row_bytes % 16 == 0 &&
+                   aligned(src_cache, 8) && aligned(dst, 16),
+               VLLM_AMD_EINVAL,
+               "gather_cache: an fp8 cache needs an entry size and strides that are multiples of 8 elements and aligned pointers");
+    if (dtype == VLLM_AMD_BF16) GC(uint2, bf16_t, true, 8); else GC(uint2, f16_t, true, 8);
+  } else {
+    // 16-byte vectors where the row, the strides and the pointers allow, single elements otherwise
+    const uint64_t all = (uint64_t)row_bytes | (uint64_t)block_bytes | (uint64_t)entry_bytes | (uint64_t)dst_row_bytes |
+                         (uint64_t)(uintptr_t)src_cache | (uint64_t)(uintptr_t)dst;
+    if (all % 16 == 0) GC(uint4, uint8_t, false, 16);
+    else if (elem_size == 4) GC(uint32_t, uint8_t, false, 4);
+    else if (elem_size == 2) GC(uint16_t, uint8_t, false, 2);
+    else GC(uint8_t, uint8_t, false, 1);
+  }
+#undef GC
+  VA_LAUNCH_CHECK("gather_cache launch");
+  return VLLM_AMD_OK;
+}

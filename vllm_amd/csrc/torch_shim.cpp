@@ -249,6 +249,30 @@ void convert_fp8(Tensor& dst_cache, const Tensor& src_cache, double scale, const
                              stream_of(src_cache)));
 }
 
+// csrc/cache_kernels.cu:675-734 (same-dtype copy; the fp8-widening form is reached through the C ABI only)
+void gather_cache(const Tensor& src_cache, Tensor& dst, const Tensor& block_table, const Tensor& cu_seq_lens,
+                  int64_t batch_size, const OptTensor& seq_starts) {
+  need_devs(src_cache, dst, block_table, cu_seq_lens, seq_starts);
+  TORCH_CHECK(block_table.scalar_type() == at::kInt, "block_table must be int32");
+  TORCH_CHECK(cu_seq_lens.scalar_type() == at::kInt, "cu_seq_lens must be int32");
+  TORCH_CHECK(!seq_starts.has_value() || seq_starts->scalar_type() == at::kInt, "seq_starts must be int32");
+  TORCH_CHECK(src_cache.scalar_type() == dst.scalar_type(), "src_cache and dst must have the same dtype");
+  TORCH_CHECK(src_cache.dim() >= 3 && dst.dim() >= 2, "gather_cache: src_cache [NUM_BLOCKS, BLOCK_SIZE, ENTRIES...], dst [TOT_TOKENS, ENTRIES...]");
+  const int64_t entry = src_cache.numel() == 0 ? 0 : src_cache.numel() / (src_cache.size(0) * src_cache.size(1));
+  TORCH_CHECK(entry > 0 && dst.numel() == dst.size(0) * entry && src_cache[0][0].is_contiguous() &&
+                  (dst.size(0) == 0 || dst[0].is_contiguous()) && block_table.dim() == 2 && block_table.stride(1) == 1 &&
+                  cu_seq_lens.is_contiguous() && cu_seq_lens.numel() > batch_size &&
+                  (!seq_starts.has_value() || (seq_starts->is_contiguous() && seq_starts->numel() >= batch_size)),
+              "gather_cache: entries of src_cache and dst must be contiguous and of one size; block_table [BATCH, "
+              "BLOCK_INDICES], cu_seq_lens [BATCH + 1], seq_starts [BATCH]");
+  DevGuard g(src_cache.device());
+  check(vllm_amd_gather_cache(src_cache.data_ptr(), dst.data_ptr(), (const int32_t*)block_table.data_ptr(),
+                              (const int32_t*)cu_seq_lens.data_ptr(), (const int32_t*)vptr(seq_starts), (int)batch_size,
+                              dst.size(0), (int)src_cache.size(1), (int)entry, block_table.stride(0),
+                              src_cache.stride(0), src_cache.stride(1), dst.stride(0), (int)src_cache.element_size(),
+                              VLLM_AMD_F32, VLLM_AMD_KV_AUTO, nullptr, stream_of(src_cache)));
+}
+
 // csrc/cache_kernels.cu:123-170; one launch per layer (no pointer table upload, no sync)
 void copy_blocks(const std::vector<Tensor>& key_caches, const std::vector<Tensor>& value_caches,
                  const Tensor& block_mapping) {
@@ -866,6 +890,11 @@ void register_all() {
        &concat_and_cache_mla);
   k.op("convert_fp8", "convert_fp8(Tensor! dst_cache, Tensor src_cache, float scale, str kv_cache_dtype) -> ()",
        &convert_fp8);
+  // csrc/torch_bindings.cpp:710-714
+  k.op("gather_cache",
+       "gather_cache(Tensor src_cache, Tensor! dst, Tensor block_table, "
+       "Tensor cu_seq_lens, int batch_size, Tensor? seq_starts) -> ()",
+       &gather_cache);
   k.op("copy_blocks",
        "copy_blocks(Tensor(a!)[] key_caches, Tensor[](b!) value_caches,"
        " Tensor block_mapping) -> ()",
